@@ -18,12 +18,22 @@ the number of ranks that answered an all-reduce, per-rank ms/step (min / max) an
 Every step renders a different one of 8 pre-generated ray batches.  Prints ONE JSON line (rank 0):
 `value` = the configs[1] training step at the random-init state (density beta 0.1, the sampler converges in one
 round) on the fp32 MFMA core, with `roofline` (dominant kernel, HIP-event timed inside the timed region;
-`traffic` read from the rocprofv3 PMC summary named beside it) and `cpu_baseline` (the CPU oracle per
-BASELINE.md section 3, rank 0, N=1 only).  Beside it, never mixed into `value` (N=1 only):
-`sharp_state` = the same step at density beta 0.01, where the sampler needs 2+ rounds, with the
-rounds per step and what the speculation of the round count cost; `hash_grid` = configs[2] with its HBM roofline;
-`alt_matrix_core` = the bf16x3 core, `alt_matrix_core_x6` = the bf16x6 core; `sustained` = a 400-step TRAINING run (closed-form scene, fused
-MonoSDFLoss, Adam, fresh rays every step, density beta 0.02 at the start: beta falls and the sampler goes to 2+ rounds).
+`traffic` read from the rocprofv3 PMC summary named beside it).  A plain run measures that and nothing else.
+
+--full adds everything that takes runs of its own: `cpu_baseline` (the CPU oracle per BASELINE.md section 3, rank 0,
+N=1 only) and, beside `value` and never mixed into it (N=1 only): `sharp_state` = the same step at density beta 0.01,
+where the sampler needs 2+ rounds, with the rounds per step and what the speculation of the round count
+cost; `hash_grid` = configs[2] with its HBM roofline; `alt_matrix_core` = the bf16x3 core, `alt_matrix_core_x6` = the
+bf16x6 core; `sustained` = a 400-step TRAINING run (closed-form scene, fused MonoSDFLoss, Adam, fresh rays every step,
+density beta 0.0125 at the start: beta falls and the sampler goes to 2+ rounds).  With N > 1 it adds the configs[2]
+gradient exchange under `multi_gpu.hash_grid`; with --config grid the hash entry points' own durations (`ms_alone`,
+5 extra steps without the side stream).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its LAST timed step computed as DIR/<name>.npy
+(float32): `out.<key>` = every floating-point tensor of the network's output dict, `loss`, `grad.<parameter>` = every
+parameter gradient.  An array of more than 2^20 elements is stored as a fixed sample of 2^20 of them (indices drawn once
+from a seeded generator, sorted; the same in every run).  Inputs are seeded: two runs with the same arguments see the
+same weights, rays and sampling noise, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -339,7 +349,35 @@ def parse_args(argv=None):
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous check without a GPU: the ranks meet over gloo on the CPU, the kernels '
                          'are skipped (a step is the flat gradient all-reduce alone), `value` is null')
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: cpu_baseline, sharp_state, hash_grid, '
+                         'alt_matrix_core*, sustained (the --no-* options above thin this out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs and gradients of the last timed step to DIR/<name>.npy (rank 0)')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 20      # larger arrays are dumped as a fixed sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_arrays(arrays, path):
+    """{name: tensor} -> path/<name>.npy in float32; an array above DUMP_MAX_ELEMS elements becomes a seeded sample."""
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        out[name] = a
+    if sum(a.nbytes for a in out.values()) > DUMP_MAX_BYTES:
+        raise RuntimeError('bench.py: --dump-outputs would write more than %d MB' % (DUMP_MAX_BYTES >> 20))
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(out.items()):
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def _free_port():
@@ -532,12 +570,13 @@ def main(argv=None):
         pose = torch.eye(4, device=device).expand(n, 4, 4).contiguous()
         return {'ray_dirs': d, 'ray_cam_loc': o, 'ray_dirs_tmp': d.clone(), 'ray_pose': pose}
 
-    def measure(precision, grid=False, beta=0.1, steps=None, fresh=False, train=False):
+    def measure(precision, grid=False, beta=0.1, steps=None, fresh=False, train=False, keep_last=False):
         """W warm-up + K timed steps of the training step on the given matrix core; returns the max over ranks.
         fresh: a different ray batch EVERY step (pre-generated on the device) instead of cycling through 8.
         train: a training run instead of the probe loss -- targets of a closed-form scene (scene_targets), the fused
         MonoSDFLoss with the weights of the reference's confs, NO warm-up steps (the run starts at the initial state);
-        the timed region is cut into windows of 100 steps (one host sync each)."""
+        the timed region is cut into windows of 100 steps (one host sync each).
+        keep_last: the result carries `last` = {name: tensor} of the last timed step (outputs, loss, gradients)."""
         steps = args.steps if steps is None else steps
         warmup = 0 if train else args.warmup
         torch.manual_seed(0)                      # same initial weights on every rank (as DDP would broadcast)
@@ -570,9 +609,11 @@ def main(argv=None):
         smp = model.ray_sampler
         rounds_seen = []
 
-        def step(i):
+        def step(i, keep=None):
             opt.zero_grad(set_to_none=True)
             out = model(batches[i % len(batches)], indices, if_pixel_input=True)
+            if keep is not None:
+                keep.update(out)
             if loss_fn is not None:           # MonoSDFLoss (model/loss.py:252-311), value + gradients in one HIP launch
                 loss = loss_fn(out, targets[i % len(batches)], if_pixel_input=True)['loss']
             else:
@@ -597,8 +638,9 @@ def main(argv=None):
         barrier()
         t0 = time.time()
         windows = []
+        last_out = {} if keep_last else None
         for i in range(steps):
-            loss = step(warmup + i)
+            loss = step(warmup + i, last_out if i == steps - 1 else None)
             if train:
                 if first_loss is None:
                     first_loss = loss           # read after the run (no sync inside the first step)
@@ -608,10 +650,16 @@ def main(argv=None):
         barrier()
         dt_own = dt = time.time() - t0
         prof, _lib.PROFILE = _lib.PROFILE, None
+        last = None
+        if keep_last:
+            last = {'out.' + k: v for k, v in last_out.items() if torch.is_tensor(v) and v.is_floating_point()}
+            last['loss'] = loss
+            last.update(('grad.' + n, p.grad) for n, p in model.named_parameters() if p.grad is not None)
+            last = {k: v.detach().cpu() for k, v in last.items()}
         if torch.is_tensor(first_loss):
             first_loss = float(first_loss.item())
         alone = None
-        if grid and world == 1:
+        if grid and world == 1 and args.full:
             # inside the step the colour network's weight-gradient launch (side stream) shares the chip with the SDF backward
             # kernel and / or the embedding scatter: their own durations, measured on 5 extra steps without the side stream
             side, ops.USE_SIDE_STREAM = ops.USE_SIDE_STREAM, False
@@ -666,7 +714,7 @@ def main(argv=None):
         return dict(dt=dt, dt_own=dt_own, steps=steps, kern=kern, rounds=hist, sampler=sampler, loss=float(loss.item()),
                     first_loss=first_loss, precision=precision, slots=(plan.hsum, plan.qsum, plan.absum), multi=multi,
                     beta_end=float(model.density.get_beta().item()), windows=windows, rounds_seq=list(rounds_seen),
-                    backward_alone_ms=alone)
+                    backward_alone_ms=alone, last=last)
 
     def mlp_rooflines(m):
         """Roofline of the dominant SDF kernel.  fp32 core: MFMA-bound (algorithmic FLOPs, SURVEY.md 8(d));
@@ -709,14 +757,16 @@ def main(argv=None):
         return world * N_RAYS * m['steps'] / m['dt']
 
     grid_only = args.config == 'grid'
-    primary = measure(args.precision, grid=grid_only, beta=args.beta)
+    primary = measure(args.precision, grid=grid_only, beta=args.beta, keep_last=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_arrays(primary['last'], args.dump_outputs)
     single = world == 1 and not use_dist
-    extras = args.extras and single and not grid_only
+    extras = args.full and args.extras and single and not grid_only
     sharp = measure(args.precision, beta=0.01) if extras else None
     alt = measure('bf16x3' if args.precision == 'fp32' else 'fp32') if (extras and args.alt_precision) else None
     alt6 = measure('bf16x6') if (extras and args.alt_precision and args.precision == 'fp32') else None
     # the hash-grid configuration: beside the headline at N = 1, and at N > 1 for its gradient exchange
-    grid = measure('fp32', grid=True) if (extras or (use_dist and args.extras and not grid_only)) else None
+    grid = measure('fp32', grid=True) if (extras or (use_dist and args.full and args.extras and not grid_only)) else None
     # density beta at the start of the `sustained` training run: just above the value at which this random-init network's
     # sampler starts to need a third round (all batches take 2 rounds at 0.014, 2-5 at 0.010), so that the falling beta
     # of the run crosses it (from the confs' 0.1 a 400-step window would stay at one round)
@@ -822,7 +872,7 @@ def main(argv=None):
                         'held to the fp32 core\'s rows of the frozen tolerance table -- on the bf16 matrix cores; weight '
                         'gradients on the fp32 kernel.  Opt-in; `value` above is the fp32 MFMA core',
             }
-        if single and not args.no_cpu_baseline:
+        if single and args.full and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()
         print(json.dumps(res))
     if use_dist:

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04prof
 mkdir -p $O
-B="python3 $R/bench.py --no-extras --no-cpu-baseline --no-alt-precision"
+B="python3 $R/bench.py --full --no-extras --no-cpu-baseline --no-alt-precision"
 for cfg in ${1:-mlp grid}; do
   EXTRA=""; CFG=$cfg
   [ "$cfg" = b16 ] && EXTRA="--precision bf16x3" && CFG=mlp

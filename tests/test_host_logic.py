@@ -349,3 +349,27 @@ def test_weight_gradient_split_plan_covers_every_point_once(P_pad):
         # the same plan every time (cached, deterministic): bitwise reproducible gradients depend on it
         again = planlib.balanced_program(build, mp, P_pad)
         assert [it['n_splits'] for it in again.items] == [it['n_splits'] for it in prog.items]
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py: a plain run is the headline alone (--full off by default), --steps < 1 is refused, and --dump-outputs
+    writes float32 .npy files, an array above DUMP_MAX_ELEMS as the same seeded sample in every run, never above 64 MB."""
+    import bench
+    a = bench.parse_args(['--steps', '7'])
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(['--full', '--dump-outputs', str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+    n = bench.DUMP_MAX_ELEMS
+    arrays = {'out.small': torch.arange(6, dtype=torch.float64).reshape(2, 3), 'grad.big': torch.arange(n + 5).float()}
+    for d in ('a', 'b'):
+        bench.dump_arrays(arrays, str(tmp_path / d))
+    small = np.load(str(tmp_path / 'a' / 'out.small.npy'))
+    assert small.dtype == np.float32 and small.shape == (2, 3) and (small == np.arange(6).reshape(2, 3)).all()
+    big_a, big_b = np.load(str(tmp_path / 'a' / 'grad.big.npy')), np.load(str(tmp_path / 'b' / 'grad.big.npy'))
+    assert big_a.dtype == np.float32 and big_a.shape == (n,) and (big_a == big_b).all()
+    assert (np.diff(big_a) > 0).all() and big_a[-1] <= n + 4
+    with pytest.raises(RuntimeError):
+        bench.dump_arrays({'a%d' % i: torch.zeros(n) for i in range(17)}, str(tmp_path / 'c'))
+    assert not (tmp_path / 'c').exists()
