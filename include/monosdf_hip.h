@@ -34,6 +34,8 @@
  *       MonoSDFLoss.forward and its backward (model/loss.py:180-311 with 29-87, 156-171).
  *   msdf_probe_loss
  *       no reference counterpart: the fixed scalar bench.py differentiates.
+ *   msdf_mc_workspace_bytes, msdf_mc_count, msdf_mc_emit
+ *       skimage.measure.marching_cubes as get_surface_sliding calls it (utils/plots.py:199-205).
  *
  * Entry points that take an msdf_plan_t run on the matrix core named by plan->precision (monosdf_plan.h).
  */
@@ -454,6 +456,22 @@ int msdf_pixel_rays(const int64_t* ray_idx, int n, const int32_t* frame_list, in
                     const float* intrinsics_all, int width, int hw, float* ray_dirs, float* ray_dirs_cam,
                     float* cam_loc, float* ray_pose, int32_t* frame_pos, const float* const* gt_src,
                     float* const* gt_dst, const int32_t* gt_channels, int n_gt, void* stream);
+
+/* ---- marching cubes (csrc/mcubes.hip; reference: skimage.measure.marching_cubes at utils/plots.py:199-205).
+ * vol: fp32 [nx, ny, nz] in C order (axis 0 = x), every dim >= 2, nx * ny * nz < 2^31.  Corners with v < level are
+ * below, the rest above; the case table is csrc/mc_tables.h (generated by scripts/gen_mc_tables.py).
+ * msdf_mc_count: classifies every cell into the caller's DEVICE workspace (msdf_mc_workspace_bytes() bytes, 16-byte
+ * aligned; -1 for dims out of range) and writes totals[0] = vertices V, totals[1] = triangles F (int64, device).
+ * msdf_mc_emit: with the workspace of a count call on the same volume and level, and V, F < 2^31: verts [V,3]
+ * (idx + t e_a) * spacing, normals [V,3] (the central-difference gradient interpolated along the edge, normalised;
+ * zero gradient -> 0), faces [F,3] int32 oriented by the right-hand rule from below toward above.  Vertices are
+ * ordered by (linear voxel index, edge axis), faces by (linear cell index, table order): no atomics, the outputs are
+ * bitwise identical run to run. */
+int64_t msdf_mc_workspace_bytes(int nx, int ny, int nz);
+int msdf_mc_count(const float* vol, int nx, int ny, int nz, float level, void* workspace, int64_t* totals,
+                  void* stream);
+int msdf_mc_emit(const float* vol, int nx, int ny, int nz, float level, float sx, float sy, float sz,
+                 const void* workspace, float* verts, float* normals, int32_t* faces, void* stream);
 
 #ifdef __cplusplus
 }

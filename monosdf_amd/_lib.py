@@ -187,6 +187,9 @@ _SIGNATURES = {
     'msdf_sampler_error_bound': [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
     'msdf_laplace_density': [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P],
     'msdf_laplace_density_backward': [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P],
+    'msdf_mc_workspace_bytes': [C.c_int, C.c_int, C.c_int],
+    'msdf_mc_count': [_P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P],
+    'msdf_mc_emit': [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P],
 }
 
 ABI_VERSION = 8

@@ -9,7 +9,8 @@
   On the GPU only the three axes of every pyramid level exist (the reference builds the 512^3 x 3 point grid
   with a CPU meshgrid and pools it), points are formed for the voxels a level's mask selects, and the volume
   leaves through a cached pinned buffer: 0.22 s per 512^3 block against 2.0 s for the reference's sequence.
-  Marching cubes itself (skimage, plots.py:199) stays with the caller.
+  ``sdf_volume_device`` yields the same blocks without leaving the device: what utils/mesh.py's
+  ``get_surface_sliding`` hands to the marching-cubes kernels (plots.py:199).
 """
 import os
 
@@ -140,12 +141,17 @@ def _to_host(t):
 
 
 def _block_on_device(evaluate, mins, maxs, cropN, device):
+    """One block of the coarse-to-fine evaluation (_volume_on_device) as a host array."""
+    return _to_host(_volume_on_device(evaluate, mins, maxs, cropN, device))
+
+
+def _volume_on_device(evaluate, mins, maxs, cropN, device):
     """One block of the coarse-to-fine evaluation with everything but the network on the device's own terms: the
     reference (plots.py:135-190) builds the cropN^3 x 3 point grid with a CPU meshgrid (3.2 GB of doubles at 512^3),
     copies 1.6 GB to the GPU and average-pools it three times; the grid is separable, so here only the three AXES of
     every pyramid level exist (the pooled coordinate of a coarse voxel is the mean of its two fine coordinates), the
-    points of a level are formed for the voxels its mask selects, and the finished volume leaves through a pinned
-    buffer.  Same masks, thresholds, nearest-neighbour upsampling and evaluation order as the reference; a pooled
+    points of a level are formed for the voxels its mask selects; the finished volume [cropN]^3 fp32 stays on the device
+    (_block_on_device takes it to the host through a pinned buffer).  Same masks, thresholds, nearest-neighbour upsampling and evaluation order as the reference; a pooled
     coordinate may differ from AvgPool3d's fp32 sum of eight in the last bit (the volume is compared with the
     reference's at 1e-4 of its range, tests/test_gpu_parity.py)."""
     # float(np.linspace in float64), the values of the reference's grid (plots.py:139-146)
@@ -172,7 +178,7 @@ def _block_on_device(evaluate, mins, maxs, cropN, device):
             mask = upsample((vals.abs() < threshold).reshape(n, n, n)[None, None].float()).bool()
             vals = upsample(vals.reshape(n, n, n)[None, None]).reshape(-1)
         threshold /= 2.
-    return _to_host(vals.reshape(cropN, cropN, cropN).float())
+    return vals.reshape(cropN, cropN, cropN).float()
 
 
 def _pyramid(points, levels=3):
@@ -185,16 +191,14 @@ def _pyramid(points, levels=3):
     return pyr[::-1]
 
 
-@torch.no_grad()
-def sdf_volume(sdf_fn, resolution=512, grid_boundary=(-1.1, 1.1), device='cuda', shard=True):
-    """Yields (origin[3], spacing[3], volume[cropN, cropN, cropN] float32 numpy) per block of the sliding
-    window, exactly the array the reference hands to marching cubes.  ``sdf_fn(points[P,3]) -> [P]``."""
+def _sliding_window(sdf_fn, resolution, grid_boundary, shard):
+    """cropN, the blocks' (mins, maxs) in (i, j, k) order (plots.py:110-133) and the block evaluation function:
+    ``sdf_fn`` over all points, or with ``shard`` over this rank's slice of them, the rows all-gathered."""
     cropN = 128 if resolution < 512 else 512
-    assert resolution % cropN == 0
+    assert resolution % cropN == 0, 'resolution: %d, cropN: %d' % (resolution, cropN)
     N = resolution // cropN
     lo, hi = grid_boundary
     edges = np.linspace(lo, hi, N + 1)
-    upsample = torch.nn.Upsample(scale_factor=2, mode='nearest')
     world, rank = (parallel.world(), parallel.rank()) if shard else (1, 0)
 
     def evaluate(pts):
@@ -206,36 +210,55 @@ def sdf_volume(sdf_fn, resolution=512, grid_boundary=(-1.1, 1.1), device='cuda',
         cuts = [parallel.shard_slice(pts.shape[0], r, world) for r in range(world)]
         return parallel.all_gather_rows(part, sizes=[hi_ - lo_ for lo_, hi_ in cuts]).reshape(-1)
 
+    blocks = [((edges[i], edges[j], edges[k]), (edges[i + 1], edges[j + 1], edges[k + 1]))
+              for i in range(N) for j in range(N) for k in range(N)]
+    return cropN, blocks, evaluate
+
+
+@torch.no_grad()
+def sdf_volume_device(sdf_fn, resolution=512, grid_boundary=(-1.1, 1.1), device='cuda', shard=True):
+    """The blocks of sdf_volume with the volume left on the device: (origin[3], spacing[3], volume[cropN, cropN, cropN]
+    float32 CUDA tensor).  The same values as sdf_volume's arrays, bit for bit."""
+    if torch.device(device).type != 'cuda':
+        raise ValueError('sdf_volume_device: device must be a CUDA device, got %r' % (device,))
+    cropN, blocks, evaluate = _sliding_window(sdf_fn, resolution, grid_boundary, shard)
+    for mins, maxs in blocks:
+        spacing = tuple((maxs[d] - mins[d]) / (cropN - 1) for d in range(3))
+        yield np.array(mins), spacing, _volume_on_device(evaluate, mins, maxs, cropN, device)
+
+
+@torch.no_grad()
+def sdf_volume(sdf_fn, resolution=512, grid_boundary=(-1.1, 1.1), device='cuda', shard=True):
+    """Yields (origin[3], spacing[3], volume[cropN, cropN, cropN] float32 numpy) per block of the sliding
+    window, exactly the array the reference hands to marching cubes.  ``sdf_fn(points[P,3]) -> [P]``."""
+    cropN, blocks, evaluate = _sliding_window(sdf_fn, resolution, grid_boundary, shard)
+    upsample = torch.nn.Upsample(scale_factor=2, mode='nearest')
     on_gpu = torch.device(device).type == 'cuda'
-    for i in range(N):
-        for j in range(N):
-            for k in range(N):
-                mins = (edges[i], edges[j], edges[k])
-                maxs = (edges[i + 1], edges[j + 1], edges[k + 1])
-                if on_gpu:
-                    spacing = tuple((maxs[d] - mins[d]) / (cropN - 1) for d in range(3))
-                    yield np.array(mins), spacing, _block_on_device(evaluate, mins, maxs, cropN, device)
-                    continue
-                # CPU (the gloo tests over the oracle's network): the reference's own sequence of tensor operations
-                axes = [torch.tensor(np.linspace(mins[d], maxs[d], cropN)) for d in range(3)]
-                xx, yy, zz = torch.meshgrid(*axes, indexing='ij')
-                pts = torch.vstack([xx.flatten(), yy.flatten(), zz.flatten()]).T.float().to(device)
-                pyr = _pyramid(pts.reshape(cropN, cropN, cropN, 3).permute(3, 0, 1, 2))
-                mask, vals = None, None
-                threshold = 2 * (maxs[0] - mins[0]) / cropN * 8
-                for pid, p in enumerate(pyr):
-                    n = p.shape[-1]
-                    flat = p.reshape(3, -1).permute(1, 0).contiguous()
-                    if mask is None:
-                        vals = evaluate(flat)
-                    else:
-                        m = mask.reshape(-1)
-                        if bool(m.any()):
-                            vals[m] = evaluate(flat[m].contiguous())
-                    if pid < 3:
-                        mask = (vals.abs() < threshold).reshape(n, n, n)[None, None]
-                        mask = upsample(mask.float()).bool()
-                        vals = upsample(vals.reshape(n, n, n)[None, None]).reshape(-1)
-                    threshold /= 2.
-                spacing = tuple((maxs[d] - mins[d]) / (cropN - 1) for d in range(3))
-                yield np.array(mins), spacing, vals.reshape(cropN, cropN, cropN).cpu().numpy().astype(np.float32)
+    for mins, maxs in blocks:
+        if on_gpu:
+            spacing = tuple((maxs[d] - mins[d]) / (cropN - 1) for d in range(3))
+            yield np.array(mins), spacing, _block_on_device(evaluate, mins, maxs, cropN, device)
+            continue
+        # CPU (the gloo tests over the oracle's network): the reference's own sequence of tensor operations
+        axes = [torch.tensor(np.linspace(mins[d], maxs[d], cropN)) for d in range(3)]
+        xx, yy, zz = torch.meshgrid(*axes, indexing='ij')
+        pts = torch.vstack([xx.flatten(), yy.flatten(), zz.flatten()]).T.float().to(device)
+        pyr = _pyramid(pts.reshape(cropN, cropN, cropN, 3).permute(3, 0, 1, 2))
+        mask, vals = None, None
+        threshold = 2 * (maxs[0] - mins[0]) / cropN * 8
+        for pid, p in enumerate(pyr):
+            n = p.shape[-1]
+            flat = p.reshape(3, -1).permute(1, 0).contiguous()
+            if mask is None:
+                vals = evaluate(flat)
+            else:
+                m = mask.reshape(-1)
+                if bool(m.any()):
+                    vals[m] = evaluate(flat[m].contiguous())
+            if pid < 3:
+                mask = (vals.abs() < threshold).reshape(n, n, n)[None, None]
+                mask = upsample(mask.float()).bool()
+                vals = upsample(vals.reshape(n, n, n)[None, None]).reshape(-1)
+            threshold /= 2.
+        spacing = tuple((maxs[d] - mins[d]) / (cropN - 1) for d in range(3))
+        yield np.array(mins), spacing, vals.reshape(cropN, cropN, cropN).cpu().numpy().astype(np.float32)
