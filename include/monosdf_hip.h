@@ -36,6 +36,12 @@
  *       no reference counterpart: the fixed scalar bench.py differentiates.
  *   msdf_mc_workspace_bytes, msdf_mc_count, msdf_mc_emit
  *       skimage.measure.marching_cubes as get_surface_sliding calls it (utils/plots.py:199-205).
+ *   msdf_nn_split_count, msdf_nn_workspace_bytes, msdf_nn_search
+ *       the all-nearest-neighbour queries of the mesh evaluation scripts: sklearn KDTree(...).query
+ *       (scannet_eval/evaluate.py:16-26) and scipy cKDTree(...).query (replica_eval/eval_recon.py:25-43, 96-106).
+ *   msdf_voxel_keys, msdf_voxel_mean
+ *       open3d PointCloud.voxel_down_sample as evaluate() calls it (scannet_eval/evaluate.py:36-38); the sort between
+ *       the two calls is the caller's.
  *
  * Entry points that take an msdf_plan_t run on the matrix core named by plan->precision (monosdf_plan.h).
  */
@@ -472,6 +478,33 @@ int msdf_mc_count(const float* vol, int nx, int ny, int nz, float level, void* w
                   void* stream);
 int msdf_mc_emit(const float* vol, int nx, int ny, int nz, float level, float sx, float sy, float sz,
                  const void* workspace, float* verts, float* normals, int32_t* faces, void* stream);
+
+/* ---- mesh evaluation (csrc/nnsearch.hip): exact nearest neighbours and the voxel down-sample.
+ * msdf_nn_search: for every query[i] (fp32 xyz, [n_query, 3]) the index idx[i] (int32) and the Euclidean distance
+ * dist[i] of the closest point of ref ([n_ref, 3] fp32), by brute force.  The squared distance is
+ * dx dx + dy dy + dz dz from the three differences, in fp32.  Of several reference points at the same fp32 squared
+ * distance the smallest index wins; outputs are bitwise the same on every call and for every split count.
+ * 1 <= n_ref < 2^31 (0 is an argument error), 0 <= n_query < 2^31 (0 launches nothing).  All coordinates must be
+ * finite: the result is undefined otherwise.  n_splits: over how many slices of the reference cloud the work is
+ * spread (partial minima merged by a second kernel); <= 0 lets the library choose from the sizes, a positive value is
+ * clamped to the number of 1024-point tiles.  msdf_nn_split_count returns the count actually used (-1 for sizes out of
+ * range).  workspace: DEVICE, msdf_nn_workspace_bytes(n_ref, n_query, n_splits) bytes for the same three values
+ * (-1 for sizes out of range), 8-byte aligned; contents are scratch.
+ * msdf_voxel_keys: keys[i] (int64) = (ix << 42) | (iy << 21) | iz of points[i] ([n, 3] fp32), with
+ * i* = floor((p - (min_bound - voxel_size / 2)) / voxel_size) per axis, every operation rounded separately in fp32;
+ * min_bound: 3 floats on the DEVICE, the per-axis minimum of the cloud.  The caller guarantees every coordinate index
+ * < 2^21 (larger ones are clamped).  voxel_size > 0.
+ * msdf_voxel_mean: with order[n] (int64) the permutation of a STABLE sort of the keys and seg_start[m] (int64) the
+ * positions in the sorted sequence where a new key begins: out[s] ([m, 3] fp32) = the mean of the points of voxel s,
+ * their fp64 sum in ascending original index over their count, rounded once to fp32.  No atomics. */
+int msdf_nn_split_count(int64_t n_ref, int64_t n_query, int n_splits);
+int64_t msdf_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int n_splits);
+int msdf_nn_search(const float* ref, int64_t n_ref, const float* query, int64_t n_query, int n_splits,
+                   void* workspace, float* dist, int32_t* idx, void* stream);
+int msdf_voxel_keys(const float* points, int64_t n, const float* min_bound, float voxel_size, int64_t* keys,
+                    void* stream);
+int msdf_voxel_mean(const float* points, const int64_t* order, const int64_t* seg_start, int64_t n, int64_t m,
+                    float* out, void* stream);
 
 #ifdef __cplusplus
 }

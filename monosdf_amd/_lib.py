@@ -190,6 +190,11 @@ _SIGNATURES = {
     'msdf_mc_workspace_bytes': [C.c_int, C.c_int, C.c_int],
     'msdf_mc_count': [_P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P],
     'msdf_mc_emit': [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P],
+    'msdf_nn_split_count': [C.c_int64, C.c_int64, C.c_int],
+    'msdf_nn_workspace_bytes': [C.c_int64, C.c_int64, C.c_int],
+    'msdf_nn_search': [_P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P, _P],
+    'msdf_voxel_keys': [_P, C.c_int64, _P, C.c_float, _P, _P],
+    'msdf_voxel_mean': [_P, _P, _P, C.c_int64, C.c_int64, _P, _P],
 }
 
 ABI_VERSION = 8
