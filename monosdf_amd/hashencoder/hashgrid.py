@@ -49,6 +49,12 @@ class HashEncoder(nn.Module):
     def log2_scale(self):
         return float(np.log2(self.per_level_scale))
 
+    @property
+    def kernel_dims(self):
+        """(levels, features per level, log2 of the per-level scale, base resolution) as the node forms of the hash
+        kernels take them (ops.GridSdfFunction, ops.hash_node_features)."""
+        return self.num_levels, self.level_dim, self.log2_scale, int(self.base_resolution)
+
     def forward(self, inputs, size=1, calc_grad_inputs=None):
         """inputs in [-size, size] -> [..., num_levels * level_dim]."""
         inputs = (inputs + size) / (2 * size)

@@ -156,11 +156,9 @@ class _SdfBase(_FusedNet):
         if self.aux_active and ops.HASH_SCATTER == 'binned' and self.encoding.level_dim > 1:
             # encoding + MLP + grid part of d sdf/dx as one autograd node: one embedding scatter per backward pass
             enc = self.encoding
-            fused.grid_offsets = enc.offsets
             sdf, _, feat, nrm, nrm_b = ops.GridSdfFunction.apply(
-                x, enc.embeddings, flat_w, flat_b, wpack, bpack, fused,
-                (enc.num_levels, enc.level_dim, enc.log2_scale, int(enc.base_resolution)), int(n_clamp), int(n_feat),
-                self.sphere_scale, bool(save), ns, float(self.divide_factor))
+                x, enc.embeddings, enc.offsets, flat_w, flat_b, wpack, bpack, fused, enc.kernel_dims, int(n_clamp),
+                int(n_feat), self.sphere_scale, bool(save), ns, float(self.divide_factor))
             feat = self._trim_features(feat)
             return (sdf, feat, nrm) if split is None else (sdf, feat, nrm, nrm_b)
         aux, handle = None, None
@@ -216,8 +214,7 @@ class _SdfBase(_FusedNet):
             if x.shape[-1] == 3 and x.dim() == 2:
                 # x01 inside the encoder kernel; the SDF kernel reads the encoder's level-major output
                 aux, aux_lm = ops.hash_node_features(
-                    x, self.divide_factor, enc.embeddings, enc.offsets,
-                    (enc.num_levels, enc.level_dim, enc.log2_scale, int(enc.base_resolution)), 16 * fused.plan.aux_tiles,
+                    x, self.divide_factor, enc.embeddings, enc.offsets, enc.kernel_dims, 16 * fused.plan.aux_tiles,
                     level_major=(fused.precision == 'fp32'))
             else:
                 with torch.no_grad():

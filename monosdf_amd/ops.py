@@ -6,6 +6,7 @@ code/model/network.py) so DDP / Adam / checkpoints keep working on ordinary
 nn.Parameters: gradients of the *effective* (weight-normalised) matrices come out
 of the kernels and flow back to weight_g / weight_v through PyTorch's own autograd.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -26,6 +27,15 @@ def _pad64(n):
     return (n + 63) // 64 * 64
 
 
+def _cont(t):
+    return None if t is None else t.contiguous()
+
+
+def _addr(t):
+    """Device address of a tensor for a pointer field of an argument struct (None -> NULL)."""
+    return None if t is None else t.data_ptr()
+
+
 # matrix core of the fused MLP kernels (include/monosdf_plan.h MSDF_PRECISION_*)
 PRECISIONS = ('fp32', 'bf16x3', 'bf16x6')      # index = MSDF_PRECISION_*
 _PLANES = {'bf16x3': 2, 'bf16x6': 3}
@@ -34,7 +44,7 @@ _PLANES = {'bf16x3': 2, 'bf16x6': 3}
 # ---------------------------------------------------------------------------
 # side stream: the colour network's weight-gradient GEMM feeds nothing but the optimiser, and the SDF network's
 # weight-gradient launch ends with a partly filled chip (1344 workgroups on 256 slots), so the two run side
-# by side.  ColorMlpFunction.backward only queues its launch; SdfMlpFunction.backward starts it on the side
+# by side.  ColorMlpFunction.backward only queues its launch; the SDF backward (_sdf_backward) starts it on the side
 # stream right after the SDF backward kernel, next to its own weight-gradient launch; the first consumer of
 # the gradients (FusedWeightNormFunction.backward) joins.  Without an SDF backward in the graph the queued
 # launch simply runs at the join, on the main stream.
@@ -187,7 +197,7 @@ class WeightNormTables:
             v = next(it)
             g = next(it) if has_g else None
             b = next(it)
-            r.v, r.g, r.b = v.data_ptr(), (g.data_ptr() if has_g else None), b.data_ptr()
+            r.v, r.g, r.b = v.data_ptr(), _addr(g), b.data_ptr()
             r.rows, r.cols = rows, cols
             r.w_off, r.b_off, r.row_off, r.has_g = w_off, b_off, b_off, int(has_g)
             recs.append(bytes(r))
@@ -285,6 +295,107 @@ def sdf_forward_nograd(mlp, wpack, bpack, x, aux, clamp_radius, sphere_scale, ru
     return out
 
 
+# what a backward pass needs to know about its forward launch besides the saved tensors.  aux_lm = (C, L C) or (0, 0);
+# jac_scale: the chain-rule factor of x -> x01 when the kernels apply the encoder's Jacobian themselves, else None
+_SdfState = collections.namedtuple(
+    '_SdfState', 'mlp P P_pad n_feat n_split saved has_aux aux_lm aux_shape jac_scale')
+
+
+def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphere_scale, save, n_split=None,
+                  aux_lm=None, aux_jac=None):
+    """The msdf_sdf_fwd_grad launch of both SDF nodes.  Returns (outputs, tensors to save, _SdfState); outputs =
+    (sdf [:n_split], sdf [n_split:], feat, d sdf/dx [:n_split], d sdf/dx [n_split:], d sdf/d aux or None), the pairs
+    being the two halves of one buffer.
+    aux_lm = (C, L C): aux, d sdf / d aux and -- in backward -- their gradients are the hash encoder's level-major
+    tensors [L, P, C] instead of rows [P, 16 * aux_tiles].
+    aux_jac = (dy_dx, k) (with aux_lm, C = 2): the encoder's Jacobian [L, P, 3, 2] and the chain-rule factor of
+    x -> x01; the kernel then adds the grid part of d sdf / d x to the returned gradient itself, and the backward
+    kernel forms the gradient arriving at d sdf / d aux from it (_sdf_backward's dy_dx and gg_out)."""
+    mp = mlp.mp
+    plan = mlp.plan
+    x = _need_cuda(x.detach(), 'points')
+    P = x.shape[0]
+    P_pad = _pad64(max(P, 1))
+    dev = x.device
+    has_aux = plan.aux_tiles > 0
+    aux = _need_cuda(aux.detach(), 'aux features') if has_aux else None
+    woff, total = planlib.sdf_workspace(mp, P_pad)
+    if not save:
+        total = woff['PM']           # only H is touched in inference
+    ws = torch.empty(max(total, 64), device=dev, dtype=torch.float32)
+    F = 16 * plan.feat_tiles
+    sdf = torch.empty(P, 1, device=dev, dtype=torch.float32)
+    # rows up to the next multiple of 64 exist (zero) so the colour network's weight-gradient GEMM
+    # can stream whole 64-point tiles of this buffer
+    feat_full = torch.empty(_pad64(max(n_feat, 1)), F, device=dev, dtype=torch.float32)
+    feat_full[n_feat:].zero_()
+    feat = feat_full[:n_feat]
+    nrm = torch.empty(P, 3, device=dev, dtype=torch.float32)
+    aC, aLC = aux_lm if (aux_lm is not None and has_aux) else (0, 0)
+    aux_shape = (aLC // aC, P, aC) if aC else (P, 16 * plan.aux_tiles)
+    r_aux = torch.empty(*aux_shape, device=dev, dtype=torch.float32) if has_aux else None
+    clamped = torch.empty(max(P, 1), device=dev, dtype=torch.uint8)
+    a = _lib.FgArgs()
+    a.wpack, a.bpack, a.x, a.aux = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr(), _addr(aux)
+    a.P, a.P_pad, a.n_clamp, a.n_feat = P, P_pad, n_clamp, n_feat
+    a.clamp_radius, a.sphere_scale = float(clamp_radius), float(sphere_scale)
+    a.sdf, a.feat, a.nrm, a.r_aux, a.clamped = sdf.data_ptr(), feat.data_ptr(), nrm.data_ptr(), _addr(r_aux), \
+        clamped.data_ptr()
+    base = ws.data_ptr()
+    a.H = base + 4 * woff['H']
+    a.PM = base + 4 * woff['PM'] if save else None
+    a.IN0 = base + 4 * woff['IN0'] if save else None
+    a.save = 1 if save else 0
+    a.aux_C, a.aux_LC = int(aC), int(aLC)
+    jac_scale = None
+    if aux_jac is not None and aC == 2:
+        jac_scale = float(aux_jac[1])
+        a.dy_dx, a.aux_dx_scale = aux_jac[0].data_ptr(), jac_scale
+    if P > 0:
+        _lib.call('msdf_sdf_fwd_grad', C.byref(plan), C.byref(a), _lib.stream_ptr())
+    ns = P if n_split is None else int(n_split)
+    state = _SdfState(mlp, P, P_pad, n_feat, ns, save, has_aux, (int(aC), int(aLC)), aux_shape, jac_scale)
+    return (sdf[:ns], sdf[ns:], feat, nrm[:ns], nrm[ns:], r_aux), (x, ws, clamped, wpack, bpack), state
+
+
+def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=None):
+    """The backward of _sdf_fwd_grad: msdf_sdf_backward, the queued side-stream work, after_sweeps, the weight
+    gradients -- in this order.  saved: the tensors _sdf_fwd_grad returned for saving; grads: one gradient (or None)
+    per output.  Returns (d loss / d aux or None, flat weight gradient [n_w + n_b]).
+    dy_dx, gg_out (state.jac_scale set): the encoder's Jacobian and the [P,3] buffer that receives jac_scale * g_nrm.
+    after_sweeps(g_aux): launches that consume d loss / d aux and should precede the weight-gradient kernels."""
+    if not state.saved:
+        raise RuntimeError('monosdf_amd: backward through an inference-mode SDF evaluation')
+    x, ws, clamped, wpack, bpack = saved
+    mlp, P, P_pad = state.mlp, state.P, state.P_pad
+    mp = mlp.mp
+    dev = x.device
+    woff, _ = planlib.sdf_workspace(mp, P_pad)
+    g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b, g_raux = [_cont(g) for g in grads]
+    g_aux = torch.empty(*state.aux_shape, device=dev, dtype=torch.float32) if state.has_aux else None
+    b = _lib.BwArgs()
+    b.aux_C, b.aux_LC = state.aux_lm
+    if state.jac_scale is not None:
+        b.dy_dx, b.aux_dx_scale, b.gg_out = dy_dx.data_ptr(), state.jac_scale, _addr(gg_out)
+    b.wpack, b.bpack, b.x = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr()
+    b.P, b.P_pad, b.n_feat, b.n_split = P, P_pad, state.n_feat, state.n_split
+    b.g_sdf, b.g_sdf_b, b.g_nrm, b.g_nrm_b = _addr(g_sdf), _addr(g_sdf_b), _addr(g_nrm), _addr(g_nrm_b)
+    b.g_feat = _addr(g_feat) if state.n_feat > 0 else None
+    b.g_raux = _addr(g_raux) if state.has_aux else None
+    b.clamped = clamped.data_ptr()
+    base = ws.data_ptr()
+    for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST'):
+        setattr(b, k, base + 4 * woff[k])
+    b.g_aux = _addr(g_aux)
+    if P > 0:
+        _lib.call('msdf_sdf_backward', C.byref(mlp.plan), C.byref(b), _lib.stream_ptr())
+        start_side_work(dev)                 # the colour network's queued weight-gradient launch, if any
+    if after_sweeps is not None:
+        after_sweeps(g_aux)
+    grad = mlp.run_wgrad(P_pad, {'ws': ws}) if P > 0 else torch.zeros(mp.n_w + mp.n_b, device=dev)
+    return g_aux, grad
+
+
 class SdfMlpFunction(torch.autograd.Function):
     """(x, aux, W, b) -> (sdf [:n_split], sdf [n_split:], feat [n_feat,F], d sdf/dx [:n_split], d sdf/dx [n_split:],
     d sdf/d aux [P,A]).  The two point groups (ray samples | eikonal points) come out as separate tensors --
@@ -293,129 +404,43 @@ class SdfMlpFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, aux, flat_w, flat_b, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius,
-                sphere_scale, save, n_split=None, aux_lm=None, aux_jac=None):
-        """aux_lm = (C, L C): aux, d sdf / d aux (the last output) and -- in backward -- their gradients are the hash
-        encoder's level-major tensors [L, P, C] instead of rows [P, 16 * aux_tiles].
-        aux_jac = (dy_dx, k) (with aux_lm, C = 2): the encoder's Jacobian [L, P, 3, 2] and the chain-rule factor of
-        x -> x01; the kernel then adds the grid part of d sdf / d x to the returned gradient itself, and the backward
-        kernel forms the gradient arriving at d sdf / d aux from it (ctx.gg_out, set by the caller, receives k * g_nrm)."""
+                sphere_scale, save, n_split=None):
         ctx.set_materialize_grads(False)
-        mp = mlp.mp
-        plan = mlp.plan
-        x = _need_cuda(x.detach(), 'points')
-        P = x.shape[0]
-        P_pad = _pad64(max(P, 1))
-        dev = x.device
-        has_aux = plan.aux_tiles > 0
-        if has_aux:
-            aux = _need_cuda(aux.detach(), 'aux features')
-        woff, total = planlib.sdf_workspace(mp, P_pad)
-        if not save:
-            total = woff['PM']           # only H is touched in inference
-        ws = torch.empty(max(total, 64), device=dev, dtype=torch.float32)
-        F = 16 * plan.feat_tiles
-        sdf = torch.empty(P, 1, device=dev, dtype=torch.float32)
-        # rows up to the next multiple of 64 exist (zero) so the colour network's weight-gradient GEMM
-        # can stream whole 64-point tiles of this buffer
-        feat_full = torch.empty(_pad64(max(n_feat, 1)), F, device=dev, dtype=torch.float32)
-        feat_full[n_feat:].zero_()
-        feat = feat_full[:n_feat]
-        nrm = torch.empty(P, 3, device=dev, dtype=torch.float32)
-        aC, aLC = aux_lm if (aux_lm is not None and has_aux) else (0, 0)
-        aux_shape = (aLC // aC, P, aC) if aC else (P, 16 * plan.aux_tiles)
-        r_aux = torch.empty(*aux_shape, device=dev, dtype=torch.float32) if has_aux else None
-        clamped = torch.empty(max(P, 1), device=dev, dtype=torch.uint8)
-        a = _lib.FgArgs()
-        a.wpack, a.bpack, a.x, a.aux = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr(), \
-            (aux.data_ptr() if has_aux else None)
-        a.P, a.P_pad, a.n_clamp, a.n_feat = P, P_pad, n_clamp, n_feat
-        a.clamp_radius, a.sphere_scale = float(clamp_radius), float(sphere_scale)
-        a.sdf, a.feat, a.nrm = sdf.data_ptr(), feat.data_ptr(), nrm.data_ptr()
-        a.r_aux = r_aux.data_ptr() if has_aux else None
-        a.clamped = clamped.data_ptr()
-        base = ws.data_ptr()
-        a.H = base + 4 * woff['H']
-        a.PM = base + 4 * woff['PM'] if save else None
-        a.IN0 = base + 4 * woff['IN0'] if save else None
-        a.save = 1 if save else 0
-        a.aux_C, a.aux_LC = int(aC), int(aLC)
-        ctx.aux_jac = None
-        if aux_jac is not None and aC == 2:
-            a.dy_dx, a.aux_dx_scale = aux_jac[0].data_ptr(), float(aux_jac[1])
-            ctx.aux_jac = (aux_jac[0], float(aux_jac[1]))
-        if P > 0:
-            _lib.call('msdf_sdf_fwd_grad', C.byref(plan), C.byref(a), _lib.stream_ptr())
-        ctx.mlp, ctx.P, ctx.P_pad, ctx.n_feat, ctx.saved = mlp, P, P_pad, n_feat, save
-        ctx.has_aux, ctx.aux_lm, ctx.aux_shape = has_aux, (int(aC), int(aLC)), aux_shape
-        ctx.n_split = ns = P if n_split is None else int(n_split)
-        ctx.save_for_backward(x, ws, clamped, wpack, bpack)
-        return sdf[:ns], sdf[ns:], feat, nrm[:ns], nrm[ns:], (r_aux if has_aux else None)
+        outs, saved, ctx.state = _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius,
+                                               sphere_scale, save, n_split)
+        ctx.save_for_backward(*saved)
+        return outs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b, g_raux):
-        if not ctx.saved:
-            raise RuntimeError('monosdf_amd: backward through an inference-mode SDF evaluation')
-        x, ws, clamped, wpack, bpack = ctx.saved_tensors
-        mlp, P, P_pad = ctx.mlp, ctx.P, ctx.P_pad
-        mp = mlp.mp
-        plan = mlp.plan
-        dev = x.device
-        woff, _ = planlib.sdf_workspace(mp, P_pad)
-        cont = lambda t: None if t is None else t.contiguous()
-        g_sdf, g_feat, g_nrm, g_raux = cont(g_sdf), cont(g_feat), cont(g_nrm), cont(g_raux)
-        g_sdf_b, g_nrm_b = cont(g_sdf_b), cont(g_nrm_b)
-        g_aux = torch.empty(*ctx.aux_shape, device=dev, dtype=torch.float32) if ctx.has_aux else None
-        b = _lib.BwArgs()
-        b.aux_C, b.aux_LC = ctx.aux_lm
-        jac = getattr(ctx, 'aux_jac', None)
-        if jac is not None:
-            gg_out = getattr(ctx, 'gg_out', None)
-            b.dy_dx, b.aux_dx_scale = jac[0].data_ptr(), jac[1]
-            b.gg_out = gg_out.data_ptr() if gg_out is not None else None
-        b.wpack, b.bpack, b.x = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr()
-        b.P, b.P_pad, b.n_feat, b.n_split = P, P_pad, ctx.n_feat, ctx.n_split
-        b.g_sdf_b = g_sdf_b.data_ptr() if g_sdf_b is not None else None
-        b.g_nrm_b = g_nrm_b.data_ptr() if g_nrm_b is not None else None
-        b.g_sdf = g_sdf.data_ptr() if g_sdf is not None else None
-        b.g_feat = g_feat.data_ptr() if (g_feat is not None and ctx.n_feat > 0) else None
-        b.g_nrm = g_nrm.data_ptr() if g_nrm is not None else None
-        b.g_raux = g_raux.data_ptr() if (g_raux is not None and ctx.has_aux) else None
-        b.clamped = clamped.data_ptr()
-        base = ws.data_ptr()
-        for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST'):
-            setattr(b, k, base + 4 * woff[k])
-        b.T = None           # the second-order term is formed again in the sweep down: no buffer
-        b.g_aux = g_aux.data_ptr() if g_aux is not None else None
-        if P > 0:
-            _lib.call('msdf_sdf_backward', C.byref(plan), C.byref(b), _lib.stream_ptr())
-            start_side_work(dev)                 # the colour network's queued weight-gradient launch, if any
-            between = getattr(ctx, 'after_sweeps', None)
-            if between is not None:
-                between(g_aux)                   # consumers of d loss / d aux that should precede the weight gradients
-            grad = mlp.run_wgrad(P_pad, {'ws': ws})
-        else:
-            between = getattr(ctx, 'after_sweeps', None)
-            if between is not None:
-                between(g_aux)
-            grad = torch.zeros(mp.n_w + mp.n_b, device=dev)
-        return (None, g_aux, grad[:mp.n_w], grad[mp.n_w:]) + (None,) * 11
+    def backward(ctx, *grads):
+        g_aux, grad = _sdf_backward(ctx.state, ctx.saved_tensors, grads)
+        n_w = ctx.state.mlp.mp.n_w
+        return (None, g_aux, grad[:n_w], grad[n_w:]) + (None,) * 9
 
 
-class _InnerCtx:
-    """Stands in for autograd's ctx when one Function runs another Function's forward / backward inside its own.
-    The tensors it is given to save are handed to the OUTER ctx.save_for_backward by the caller (autograd's
-    in-place version check then covers them) and put back before the inner backward runs."""
-
-    def __init__(self):
-        self.saved_tensors = ()
-        self.after_sweeps = None
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def set_materialize_grads(self, flag):
-        pass
+def _encode_points(x, divide_factor, embeddings, offsets, enc, pitch, level_major, jacobian):
+    """msdf_hash_node_forward on the points x (world coordinates; x01 is formed inside the encoder kernel).
+    Returns (x, features, aux_lm, x01, dy_dx) with x as the kernels read it.  features: the encoder's level-major
+    [L, B, C] tensor with aux_lm = (C, L C) -- two features per level (every configuration of the reference) and
+    level_major: the SDF kernels read and write that layout themselves -- else rows of `pitch` floats (one LDS-tiled
+    transpose) with aux_lm = None.  jacobian: also x01 [B, 3] and the Jacobian dy_dx [L, B, 3, C] (else None)."""
+    x = _need_cuda(x.detach(), 'points')
+    emb = _need_cuda(embeddings.detach(), 'embeddings')
+    L, Cdim, S, H = enc
+    B, D = x.shape
+    dev = x.device
+    x01 = torch.empty(B, D, device=dev, dtype=torch.float32) if jacobian else None
+    outputs = torch.empty(L, B, Cdim, device=dev, dtype=torch.float32)
+    dy_dx = torch.empty(B, L * D * Cdim, device=dev, dtype=torch.float32) if jacobian else None
+    st = _lib.stream_ptr()
+    _lib.call('msdf_hash_node_forward', _lib.ptr(x), float(divide_factor), _lib.ptr(x01), _lib.ptr(emb),
+              _lib.ptr(offsets), _lib.ptr(outputs), 0, B, Cdim, L, S, H, _lib.ptr(dy_dx), st)
+    if Cdim == 2 and level_major:
+        return x, outputs, (Cdim, L * Cdim), x01, dy_dx
+    aux = torch.empty(B, pitch, device=dev, dtype=torch.float32)
+    _lib.call('msdf_hash_transpose', _lib.ptr(outputs), _lib.ptr(aux), None, None, L, B, Cdim, pitch, 1, st)
+    return x, aux, None, x01, dy_dx
 
 
 class GridSdfFunction(torch.autograd.Function):
@@ -425,80 +450,56 @@ class GridSdfFunction(torch.autograd.Function):
     As three nodes (encode -> MLP -> grid part of d sdf/dx) the backward pass scatters into the embedding table
     twice: the second-order term when the gradient of d sdf/dx arrives, the first-order term after the MLP's
     backward kernel.  Both visit the same corners of the same points, so here they are ONE binned scatter
-    (msdf_hash_encode_backward_fused) at the end of the node's backward."""
+    (msdf_hash_node_scatter), launched between the SDF backward kernel and its weight-gradient kernels."""
 
     @staticmethod
-    def forward(ctx, x, embeddings, flat_w, flat_b, wpack, bpack, mlp, enc, n_clamp, n_feat, sphere_scale, save,
-                n_split, divide_factor):
+    def forward(ctx, x, embeddings, offsets, flat_w, flat_b, wpack, bpack, mlp, enc, n_clamp, n_feat, sphere_scale,
+                save, n_split, divide_factor):
+        """enc: HashEncoder.kernel_dims; offsets: its level offsets table."""
         ctx.set_materialize_grads(False)
-        x = _need_cuda(x.detach(), 'points')
-        emb = _need_cuda(embeddings.detach(), 'embeddings')
-        B, D = x.shape
         L, Cdim, S, H = enc
-        offsets = mlp.grid_offsets
         A = 16 * mlp.plan.aux_tiles                 # row pitch of the grid features as the SDF kernels read them
-        # the node forms of the hash kernels (csrc/hashgrid.hip): x01 formed inside the encoder kernel, which writes its
-        # own level-major [L, B, C] output and the Jacobian dy_dx [L, B, 3, C]
-        x01 = torch.empty(B, D, device=x.device, dtype=torch.float32)
-        outputs = torch.empty(L, B, Cdim, device=x.device, dtype=torch.float32)
-        dy_dx = torch.empty(B, L * D * Cdim, device=x.device, dtype=torch.float32)
-        st = _lib.stream_ptr()
-        _lib.call('msdf_hash_node_forward', _lib.ptr(x), float(divide_factor), _lib.ptr(x01), _lib.ptr(emb),
-                  _lib.ptr(offsets), _lib.ptr(outputs), 0, B, Cdim, L, S, H, _lib.ptr(dy_dx), st)
-        # two features per level (every configuration of the reference): the SDF kernels read and write the encoder's
-        # level-major tensors themselves; other channel counts go through rows and the LDS-tiled transpose
-        lm = (Cdim, L * Cdim) if (Cdim == 2 and mlp.precision == 'fp32') else None      # the bf16 cores take rows
-        if lm is not None:
-            aux = outputs
-        else:
-            aux = torch.empty(B, A, device=x.device, dtype=torch.float32)
-            _lib.call('msdf_hash_transpose', _lib.ptr(outputs), _lib.ptr(aux), None, None, L, B, Cdim, A, 1, st)
-        inner = _InnerCtx()
+        # the bf16 cores take rows
+        x, aux, lm, x01, dy_dx = _encode_points(x, divide_factor, embeddings, offsets, enc, A,
+                                                mlp.precision == 'fp32', True)
+        B = x.shape[0]
         # d sdf / d x through the grid: sum_{l,c} (d sdf / d feature) * d feature / d x01, chain rule to x, added to the
         # MLP's own d sdf / d x -- inside the SDF kernel with the level-major tensors (FUSE_JACOBIAN), otherwise by
         # msdf_hash_node_input_gradient in place (nrm_a / nrm_b are the two halves of ONE [B,3] buffer starting at nrm_a)
         k = 0.5 / divide_factor
         jac = (dy_dx, k) if (lm is not None and FUSE_JACOBIAN) else None
         # the grid class never clamps (network.py:290-309): clamp radius 0
-        sdf_a, sdf_b, feat, nrm_a, nrm_b, r_aux = SdfMlpFunction.forward(
-            inner, x, aux, flat_w, flat_b, wpack, bpack, mlp, n_clamp, n_feat, 0.0, sphere_scale, save, n_split, lm, jac)
+        (sdf_a, sdf_b, feat, nrm_a, nrm_b, r_aux), saved, ctx.state = _sdf_fwd_grad(
+            x, aux, wpack, bpack, mlp, n_clamp, n_feat, 0.0, sphere_scale, save, n_split, lm, jac)
         if jac is None:
             assert nrm_a.data_ptr() + 12 * nrm_a.shape[0] == nrm_b.data_ptr() or nrm_b.shape[0] == 0
             _lib.call('msdf_hash_node_input_gradient', _lib.ptr(r_aux), 0 if lm is not None else A, _lib.ptr(dy_dx), B,
-                      Cdim, L, float(k), _lib.ptr(nrm_a), st)
-        ctx.inner, ctx.enc, ctx.k, ctx.n_entries, ctx.lm = inner, enc, k, emb.shape[0], lm
-        ctx.offsets = offsets
-        ctx.save_for_backward(x01, dy_dx, r_aux, *inner.saved_tensors)
-        inner.saved_tensors = ()
+                      Cdim, L, float(k), _lib.ptr(nrm_a), _lib.stream_ptr())
+        ctx.enc, ctx.k, ctx.n_entries, ctx.lm, ctx.offsets = enc, k, embeddings.shape[0], lm, offsets
+        ctx.save_for_backward(x01, dy_dx, r_aux, *saved)
         return sdf_a, sdf_b, feat, nrm_a, nrm_b
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b):
-        x01, dy_dx, r_aux, *inner_saved = ctx.saved_tensors
-        inner, (L, Cdim, S, H), k = ctx.inner, ctx.enc, ctx.k
-        inner.saved_tensors = tuple(inner_saved)
+        x01, dy_dx, r_aux, *saved = ctx.saved_tensors
+        state, (L, Cdim, S, H), k, lm = ctx.state, ctx.enc, ctx.k, ctx.lm
         B, D = x01.shape
         dev = x01.device
-        ns = inner.n_split
         st = _lib.stream_ptr()
-        A = 16 * inner.mlp.plan.aux_tiles
+        A = 16 * state.mlp.plan.aux_tiles
         # gradient arriving at the grid part of d sdf/dx (the reference's grad_grad_inputs, hashgrid.py:71-84), scaled
         # by the chain-rule factor, and its term for d sdf / d feature: grad_grad[b, l C + c] = sum_d gg[b,d] dy_dx --
         # one launch, written as the rows the SDF backward kernel reads
-        lm = ctx.lm
         gg = torch.empty(B, D, device=dev, dtype=torch.float32)
-        if getattr(inner, 'aux_jac', None) is not None:
+        if state.jac_scale is not None:
             # the SDF backward kernel forms this gradient from dy_dx itself and writes gg (k * g_nrm) for the scatter
             g_raux = None
-            inner.gg_out = gg
         else:
             g_raux = torch.empty(*((L, B, Cdim) if lm is not None else (B, A)), device=dev, dtype=torch.float32)
-            cont = lambda t: None if t is None else t.contiguous()
-            g_nrm_c, g_nrm_b_c = cont(g_nrm), cont(g_nrm_b)
-            _lib.call('msdf_hash_node_second_grad', _lib.ptr(g_nrm_c) if g_nrm_c is not None else None,
-                      _lib.ptr(g_nrm_b_c) if g_nrm_b_c is not None else None, ns, float(k), _lib.ptr(gg), _lib.ptr(dy_dx),
-                      _lib.ptr(g_raux), 0 if lm is not None else A, B, Cdim, L, st)
+            _lib.call('msdf_hash_node_second_grad', _lib.ptr(_cont(g_nrm)), _lib.ptr(_cont(g_nrm_b)), state.n_split,
+                      float(k), _lib.ptr(gg), _lib.ptr(dy_dx), _lib.ptr(g_raux), 0 if lm is not None else A, B, Cdim,
+                      L, st)
         done = []
 
         def scatter(g_aux):
@@ -523,37 +524,19 @@ class GridSdfFunction(torch.autograd.Function):
             parallel.mark_grad_ready(g_emb)
             done.append(g_emb)
 
-        inner.after_sweeps = scatter
-        try:
-            res = SdfMlpFunction.backward(inner, g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b, g_raux)
-        finally:
-            inner.after_sweeps = None
-            inner.saved_tensors = ()
-            inner.gg_out = None
-        g_w, g_b = res[2], res[3]
+        _, grad = _sdf_backward(state, saved, (g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b, g_raux), dy_dx=dy_dx, gg_out=gg,
+                                after_sweeps=scatter)
+        n_w = state.mlp.mp.n_w
         # the only reference to the table gradient leaves with the return value: autograd then adopts the tensor as
         # embeddings.grad instead of copying 48.8 MB
-        return (None, done.pop(), g_w, g_b) + (None,) * 10
+        return (None, done.pop(), None, grad[:n_w], grad[n_w:]) + (None,) * 10
 
 
 def hash_node_features(x, divide_factor, embeddings, offsets, enc, pitch, level_major=True):
     """Grid features of the points x (world coordinates), no gradient: what the sampler's SDF evaluations feed the fused
-    forward kernel -- x01 inside the encoder kernel.  Returns (tensor, aux_lm): the encoder's level-major [L, B, C]
-    tensor with aux_lm = (C, L C) for two features per level, else rows of `pitch` floats (one LDS-tiled transpose)
-    with aux_lm = None."""
-    x = _need_cuda(x.detach(), 'points')
-    emb = _need_cuda(embeddings.detach(), 'embeddings')
-    L, Cdim, S, H = enc
-    B = x.shape[0]
-    st = _lib.stream_ptr()
-    outputs = torch.empty(L, B, Cdim, device=x.device, dtype=torch.float32)
-    _lib.call('msdf_hash_node_forward', _lib.ptr(x), float(divide_factor), None, _lib.ptr(emb), _lib.ptr(offsets),
-              _lib.ptr(outputs), 0, B, Cdim, L, S, H, None, st)
-    if Cdim == 2 and level_major:
-        return outputs, (Cdim, L * Cdim)          # the SDF kernel reads the level-major tensor itself
-    aux = torch.empty(B, pitch, device=x.device, dtype=torch.float32)
-    _lib.call('msdf_hash_transpose', _lib.ptr(outputs), _lib.ptr(aux), None, None, L, B, Cdim, pitch, 1, st)
-    return aux, None
+    forward kernel.  Returns (tensor, aux_lm) as _encode_points does."""
+    _, aux, aux_lm, _, _ = _encode_points(x, divide_factor, embeddings, offsets, enc, pitch, level_major, False)
+    return aux, aux_lm
 
 
 # ---------------------------------------------------------------------------
@@ -603,7 +586,7 @@ class ColorMlpFunction(torch.autograd.Function):
         a = _lib.ColorFwdArgs()
         a.wpack, a.bpack = wpack.data_ptr(), bpack.data_ptr()
         a.x, a.dirs, a.nrm, a.feat = x.data_ptr(), dirs.data_ptr(), nrm.data_ptr(), feat.data_ptr()
-        a.code = code.data_ptr() if has_code else None
+        a.code = _addr(code) if has_code else None
         a.P, a.P_pad, a.spr, a.save = P, P_pad, int(spr), 1 if save else 0
         a.rgb = rgb.data_ptr()
         base = ws.data_ptr()
@@ -636,7 +619,7 @@ class ColorMlpFunction(torch.autograd.Function):
         b.H, b.AB = base + 4 * woff['H'], base + 4 * woff['AB']
         b.g_feat, b.g_misc = g_feat.data_ptr(), g_misc.data_ptr()
         g_nrm = torch.empty(P, 3, device=dev, dtype=torch.float32) if plan.mode == 1 else None
-        b.g_nrm = g_nrm.data_ptr() if g_nrm is not None else None
+        b.g_nrm = _addr(g_nrm)
         if P > 0:
             _lib.call('msdf_color_backward', C.byref(plan), C.byref(b), _lib.stream_ptr())
             grad = cmlp.run_wgrad(P_pad, {'ws': ws, 'feat': feat}, defer=USE_SIDE_STREAM)
@@ -697,7 +680,7 @@ class CompositeFunction(torch.autograd.Function):
         a.z, a.sdf, a.rgb, a.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
         a.beta, a.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
         a.depth_scale_stride = ds_stride
-        a.depth_vals = depth_vals.data_ptr() if depth_vals is not None else None
+        a.depth_vals = _addr(depth_vals)
         a.N, a.S, a.white_bkgd = N, S, 1 if white_bkgd else 0
         a.bg0, a.bg1, a.bg2 = [float(v) for v in bg]
         a.weights, a.rgb_values, a.depth_values = weights.data_ptr(), rgb_values.data_ptr(), depth_values.data_ptr()
@@ -725,8 +708,7 @@ class CompositeFunction(torch.autograd.Function):
         z, sdf, rgb, nrm, beta, depth_scale, weights, wsum, depth_values, pose, raw = ctx.saved_tensors
         N, S = z.shape
         dev = z.device
-        cont = lambda t: None if t is None else t.contiguous()
-        g_w, g_rgbv, g_depth, g_nmap = cont(g_w), cont(g_rgbv), cont(g_depth), cont(g_nmap)
+        g_w, g_rgbv, g_depth, g_nmap = _cont(g_w), _cont(g_rgbv), _cont(g_depth), _cont(g_nmap)
         g_sdf = torch.empty(N, S, device=dev)
         g_rgb = torch.empty(N, S, 3, device=dev)
         g_nrm = torch.empty(N, S, 3, device=dev)
@@ -735,10 +717,7 @@ class CompositeFunction(torch.autograd.Function):
         b.z, b.sdf, b.rgb, b.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
         b.beta, b.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
         b.weights, b.wsum, b.depth_values = weights.data_ptr(), wsum.data_ptr(), depth_values.data_ptr()
-        b.g_rgb_values = g_rgbv.data_ptr() if g_rgbv is not None else None
-        b.g_depth = g_depth.data_ptr() if g_depth is not None else None
-        b.g_normal = g_nmap.data_ptr() if g_nmap is not None else None
-        b.g_weights = g_w.data_ptr() if g_w is not None else None
+        b.g_rgb_values, b.g_depth, b.g_normal, b.g_weights = _addr(g_rgbv), _addr(g_depth), _addr(g_nmap), _addr(g_w)
         b.N, b.S, b.white_bkgd = N, S, 1 if ctx.white_bkgd else 0
         b.bg0, b.bg1, b.bg2 = ctx.bg
         b.g_sdf, b.g_rgb, b.g_nrm, b.g_beta_part = g_sdf.data_ptr(), g_rgb.data_ptr(), g_nrm.data_ptr(), \
@@ -921,6 +900,27 @@ class HashEncodeWithJacobian(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # fused benchmark loss (value + gradients in one launch)
 # ---------------------------------------------------------------------------
+def _flat_grad_views(like):
+    """One flat buffer and a view of it shaped like each tensor of `like`: the loss kernels write their gradients
+    through the views, the backward scales all of them with ONE multiply (_scaled_views)."""
+    flat = torch.empty(sum(t.numel() for t in like), device=like[0].device, dtype=torch.float32)
+    views, off = [], 0
+    for t in like:
+        views.append(flat[off:off + t.numel()].view(t.shape))
+        off += t.numel()
+    return flat, views
+
+
+def _scaled_views(flat, g, shapes):
+    """flat * g, cut into tensors of the given shapes (those of _flat_grad_views)."""
+    scaled = flat * g
+    res, off = [], 0
+    for shape in shapes:
+        res.append(scaled[off:off + shape.numel()].view(shape))
+        off += shape.numel()
+    return res
+
+
 class ProbeLossFunction(torch.autograd.Function):
     """mean|rgb| + w_n mean|normal| + w_d mean depth + w_e mean (|g1|-1)^2 + w_s mean |n1 - n2|  (BASELINE.md 2)."""
 
@@ -931,13 +931,7 @@ class ProbeLossFunction(torch.autograd.Function):
         g1, g2 = _need_cuda(g1.detach(), 'grad_theta'), _need_cuda(g2.detach(), 'grad_theta_nei')
         N, M = rgb.shape[0], g1.shape[0]
         dev = rgb.device
-        # the five gradient tensors are views of one buffer: the backward scales them with ONE multiply
-        sizes = [t.numel() for t in (rgb, nrm, depth, g1, g2)]
-        flat = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-        outs, off = [], 0
-        for t, n in zip((rgb, nrm, depth, g1, g2), sizes):
-            outs.append(flat[off:off + n].view(t.shape))
-            off += n
+        flat, outs = _flat_grad_views((rgb, nrm, depth, g1, g2))
         partial = torch.empty(1, device=dev, dtype=torch.float32)        # the complete loss value (one workgroup)
         a = _lib.ProbeLossArgs()
         a.rgb, a.nrm, a.depth, a.g1, a.g2 = [t.data_ptr() for t in (rgb, nrm, depth, g1, g2)]
@@ -947,18 +941,14 @@ class ProbeLossFunction(torch.autograd.Function):
         a.partial = partial.data_ptr()
         _lib.call('msdf_probe_loss', C.byref(a), _lib.stream_ptr())
         ctx.save_for_backward(flat)
-        ctx.sizes, ctx.shapes = sizes, [t.shape for t in (rgb, nrm, depth, g1, g2)]
+        ctx.shapes = [t.shape for t in outs]
         return partial.reshape(())
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         flat, = ctx.saved_tensors
-        scaled = flat * g
-        res, off = [], 0
-        for n, shape in zip(ctx.sizes, ctx.shapes):
-            res.append(scaled[off:off + n].view(shape))
-            off += n
+        res = _scaled_views(flat, g, ctx.shapes)
         res[2] = res[2].reshape(-1, 1)
         return tuple(res) + (None, None, None, None)
 
@@ -1017,41 +1007,29 @@ class MonoSdfLossFunction(torch.autograd.Function):
             raise RuntimeError('monosdf_amd: ground-truth tensors do not match the %d rays of the batch' % N)
         out = torch.empty(8, device=dev, dtype=torch.float32)
         mask = torch.empty(N, device=dev, dtype=torch.float32)
-        # the gradient tensors are views of one buffer: the backward scales them with ONE multiply
-        like = [rgb, depth, normal] + ([g1, g2] if has_eik else [])
-        sizes = [t.numel() for t in like]
-        flat = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-        grads, off = [], 0
-        for t, n in zip(like, sizes):
-            grads.append(flat[off:off + n].view(t.shape))
-            off += n
+        flat, grads = _flat_grad_views([rgb, depth, normal] + ([g1, g2] if has_eik else []))
         a = _lib.MonoSdfLossArgs()
         a.rgb, a.depth, a.normal, a.sdf = rgb.data_ptr(), depth.data_ptr(), normal.data_ptr(), sdf.data_ptr()
-        a.grad_theta = g1.data_ptr() if has_eik else None
-        a.grad_nei = g2.data_ptr() if has_eik else None
         a.rgb_gt, a.depth_gt, a.normal_gt, a.mask_gt = [t.data_ptr() for t in data]
         a.N, a.S, a.E = N, sdf.shape[1], (g1.shape[0] if has_eik else 0)
         a.gamma, a.scale_invariant = int(bool(gamma)), int(bool(scale_invariant))
         a.w_eik, a.w_smooth, a.w_depth, a.w_nl1, a.w_ncos = [float(w) for w in weights]
         a.mask, a.out = mask.data_ptr(), out.data_ptr()
         a.g_rgb, a.g_depth, a.g_normal = [t.data_ptr() for t in grads[:3]]
-        a.g_theta = grads[3].data_ptr() if has_eik else None
-        a.g_nei = grads[4].data_ptr() if has_eik else None
+        if has_eik:
+            a.grad_theta, a.grad_nei = g1.data_ptr(), g2.data_ptr()
+            a.g_theta, a.g_nei = grads[3].data_ptr(), grads[4].data_ptr()
         _lib.call('msdf_monosdf_loss', C.byref(a), _lib.stream_ptr())
         ctx.has_eik = has_eik
         ctx.save_for_backward(flat)
-        ctx.sizes, ctx.shapes = sizes, [t.shape for t in like]
+        ctx.shapes = [t.shape for t in grads]
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
         flat, = ctx.saved_tensors
-        scaled = flat * g_out[0]
-        res, off = [], 0
-        for n, shape in zip(ctx.sizes, ctx.shapes):
-            res.append(scaled[off:off + n].view(shape))
-            off += n
+        res = _scaled_views(flat, g_out[0], ctx.shapes)
         res[1] = res[1].reshape(ctx.depth_shape)
         if not ctx.has_eik:
             res += [None, None]

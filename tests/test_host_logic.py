@@ -224,7 +224,7 @@ def test_tolerance_table_is_frozen_and_bounded(capsys):
 
 
 def test_flat_gradient_needs_a_zero_fill_only_where_the_reduce_rules_leave_holes():
-    """ops.MlpShared.run_wgrad allocates the flat weight gradient without a zero fill when the reduce rules store to
+    """ops.FusedMlp.run_wgrad allocates the flat weight gradient without a zero fill when the reduce rules store to
     every element (WgradProgram.writes_every_element): true for the networks of the reference's configurations, false
     for the fork's "MLP" configuration of the grid class, whose inactive grid-feature columns no rule writes."""
     import bench
