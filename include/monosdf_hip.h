@@ -506,6 +506,41 @@ int msdf_voxel_keys(const float* points, int64_t n, const float* min_bound, floa
 int msdf_voxel_mean(const float* points, const int64_t* order, const int64_t* seg_start, int64_t n, int64_t m,
                     float* out, void* stream);
 
+/* ---- mesh re-fusion (csrc/refuse.hip; reference: scannet_eval/evaluate.py:111-137, postprocess/refuse.py,
+ * replica_eval/cull_mesh.py:58-87).  Cameras are OpenCV-style (x right, y down, z forward).  w2c: [n_views, 12] fp32 on
+ * the DEVICE, the first three rows of the world-to-camera matrix of every view, row-major (r00 r01 r02 tx ...).
+ * No floating-point atomics anywhere: outputs are bitwise identical run to run.
+ * msdf_raster_depth: depth [n_views, height, width] fp32 = camera-frame z of the nearest intersection of the ray through
+ * ((j + pixel_center - cx) / fx, (i + pixel_center - cy) / fy, 1) with any face (both windings) of the mesh verts
+ * [n_verts, 3] fp32 (world) / faces [n_faces, 3] int32, among intersections with znear <= z <= zfar; 0 where there is
+ * none.  Two faces that share an edge leave no crack between them.  A face with an index outside [0, n_verts) or
+ * without area touches no pixel; n_faces = 0 gives zeros.  0 < znear <= zfar, n_views <= 65535, height * width < 2^31.
+ * msdf_tsdf_integrate: a dense block of nx x ny x nz voxels (C order, < 2^31), voxel (i, j, k) centred at
+ * o + voxel_length (i + i0 + 0.5, j + j0 + 0.5, k + k0 + 0.5) ((i0, j0, k0) >= 0: where the block starts in a larger
+ * volume with origin o; index + offset < 2^24, exact in fp32, so a voxel that two blocks share has the same centre
+ * in both), fused from the depth maps [n_views, height, width] in the order given
+ * by the rule of open3d's UniformTSDFVolume (separately rounded fp32 operations): p = R x + t, skipped unless p.z > 0;
+ * u = int(fx p.x / p.z + cx + 0.5), v likewise, skipped outside the image; d = depth[v, u], skipped unless
+ * 0 < d <= depth_trunc; s = (d - p.z) |((u - cx) / fx, (v - cy) / fy, 1)|, skipped if s <= -sdf_trunc;
+ * tsdf = (tsdf w + min(1, s / sdf_trunc)) / (w + 1), w += 1, from tsdf = w = 0 (resume = 0) or from what tsdf and
+ * weight hold (resume = 1: a further chunk of the same list of views).  Outputs tsdf, weight [nx, ny, nz].
+ * msdf_tsdf_face_keep: keep[f] (uint8) = 1 iff every lattice point in [floor(min), ceil(max)] per axis of the three
+ * vertices of face f (verts in index units, as marching cubes gives them with spacing 1) has weight > 0; 0 for a face
+ * with a vertex outside the lattice or an index outside [0, n_verts).
+ * msdf_cull_vertices: seen[i] (uint8) = 1 iff for some view, with p = R x + t: p.z >= 1e-5 and
+ * 0 < fx p.x / (p.z - 1e-5) + cx < width and 0 < fy p.y / (p.z - 1e-5) + cy < height (separately rounded fp32). */
+int msdf_raster_depth(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* w2c,
+                      int n_views, float fx, float fy, float cx, float cy, int height, int width, float znear,
+                      float zfar, float pixel_center, float* depth, void* stream);
+int msdf_tsdf_integrate(const float* depth, const float* w2c, int n_views, float fx, float fy, float cx, float cy,
+                        int height, int width, float ox, float oy, float oz, int i0, int j0, int k0, int nx, int ny,
+                        int nz, float voxel_length, float sdf_trunc, float depth_trunc, int resume, float* tsdf,
+                        float* weight, void* stream);
+int msdf_tsdf_face_keep(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                        const float* weight, int nx, int ny, int nz, uint8_t* keep, void* stream);
+int msdf_cull_vertices(const float* verts, int64_t n_verts, const float* w2c, int n_views, float fx, float fy, float cx,
+                       float cy, int height, int width, uint8_t* seen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

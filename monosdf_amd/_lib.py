@@ -195,6 +195,14 @@ _SIGNATURES = {
     'msdf_nn_search': [_P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P, _P],
     'msdf_voxel_keys': [_P, C.c_int64, _P, C.c_float, _P, _P],
     'msdf_voxel_mean': [_P, _P, _P, C.c_int64, C.c_int64, _P, _P],
+    'msdf_raster_depth': [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                          C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P],
+    'msdf_tsdf_integrate': [_P, _P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                            C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                            C.c_float, C.c_float, C.c_float, C.c_int, _P, _P, _P],
+    'msdf_tsdf_face_keep': [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P],
+    'msdf_cull_vertices': [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                           _P, _P],
 }
 
 ABI_VERSION = 8

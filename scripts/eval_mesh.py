@@ -6,8 +6,8 @@ scannet: evaluate() of scannet_eval/evaluate.py (vertex clouds, 2 cm voxel down-
 replica: the metrics of calc_3d_metric() of replica_eval/eval_recon.py (200,000 surface samples per mesh, 5 cm).
 --scale-mat: a cameras.npz whose `scale_mat_0` takes the predicted mesh from the normalised training frame to the
 world frame (evaluation/eval.py applies it before it writes the mesh; pass it when PRED.ply was written without).
-The meshes must be aligned already: ICP, the bounding-box crop, view culling and TSDF re-fusion are not done here
-(monosdf_amd/utils/mesh_eval.py).
+The meshes must be aligned already: ICP and the bounding-box crop are not done here (monosdf_amd/utils/mesh_eval.py).
+The reference scores the re-fused (ScanNet) or frustum-culled (Replica) mesh: make PRED.ply with scripts/refuse_mesh.py.
 """
 import argparse
 import json
