@@ -66,7 +66,32 @@ int msdf_abi_version(void);
 /* ---- hash grid (reference: hashencoder/src/hashencoder.h:13-15) ----
  * calc_grad_inputs: 0 / 1 as in the reference (dy_dx laid out [B, L, 3 C]); 2 = the same with dy_dx level-major
  * [L, B, 3 C], which every kernel here reads and writes as contiguous rows -- a caller that owns dy_dx end to end
- * passes 2 to all three calls. */
+ * passes 2 to all three calls.
+ *
+ * Return codes of the seven entry points that produce a table (embedding) gradient -- msdf_hash_encode_backward,
+ * _second_backward, _backward_ws, _second_backward_ws, _backward_fused, _backward_fused_out, msdf_hash_node_scatter.
+ * The tests are made in this order, the first that fails decides, and a refused call launches nothing: the table
+ * gradient is left untouched.
+ *
+ *   1  D != 3 (entries that take D)                                          MSDF_ERR_UNSUPPORTED
+ *   2  C not 1, 2, 4 or 8; C == 1 in anything second-order (every entry
+ *      but _backward and _backward_ws: the reference has none either)        MSDF_ERR_UNSUPPORTED
+ *   3  _fused, _fused_out: grad_embeddings, grad_first, grad_second or
+ *      grad_grad_inputs NULL; node_scatter: grad_embeddings NULL             MSDF_ERR_ARG
+ *   4  B == 0: nothing is read, the other pointers may be NULL               MSDF_OK
+ *      ("=" forms, _fused_out and node_scatter: the table gradient is set to zero; "+=" forms: untouched)
+ *   5  a NULL operand of a requested output (below); pitch != 0 and
+ *      pitch < L*C (node_scatter)                                            MSDF_ERR_ARG
+ *   6  a table of n_entries*C >= 2^31 floats or B*L*8 >= 2^31 corner
+ *      records (the binned entries: all but _backward, _second_backward)     MSDF_ERR_UNSUPPORTED
+ *   7  workspace NULL, not 16-byte aligned, or shorter than
+ *      msdf_hash_scatter_workspace_bytes(B, C, L, n_entries)                 MSDF_ERR_ARG
+ *
+ * Outputs and operands of the four reference-order entries: a NULL grad_embeddings / grad2_embeddings / grad_grad
+ * skips that output (calc_grad_inputs == 0 skips grad_inputs), and with it the workspace is not looked at.  The table
+ * gradient needs grad, inputs, offsets (and grad_grad_inputs, second order); grad_inputs needs grad and dy_dx;
+ * grad_grad needs grad_grad_inputs and dy_dx.  node_scatter needs its three operands, inputs and offsets.
+ * `embeddings` is never read.  MSDF_ERR_LAUNCH: the runtime refused a launch. */
 int msdf_hash_encode_forward(const float* inputs, const float* embeddings, const int* offsets, float* outputs,
                              uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                              int calc_grad_inputs, float* dy_dx, void* stream);
@@ -81,7 +106,7 @@ int msdf_hash_encode_second_backward(const float* grad, const float* inputs, con
                                      void* stream);
 
 /* The same two gradients with the embedding scatter summed per table slice in LDS instead of one memory-side float
- * atomic per corner (csrc/hashgrid.hip "Binned scatter"): the argument lists above, followed by the number of rows of
+ * atomic per corner (csrc/hash_scatter.h "Binned scatter"): the argument lists above, followed by the number of rows of
  * the embedding table and a caller-owned DEVICE workspace of at least msdf_hash_scatter_workspace_bytes() bytes
  * (16-byte aligned; contents are scratch, nothing persists between calls).  Results equal the plain entry points up
  * to the order of the fp32 sums. */

@@ -508,8 +508,7 @@ class GridSdfFunction(torch.autograd.Function):
             exchanges it under the weight-gradient kernels (parallel.GradientAverager)."""
             # the "=" form: the table gradient is written, not added to -- no 48.8 MB zero fill, no read of the table
             g_emb = torch.empty(ctx.n_entries, Cdim, device=dev, dtype=torch.float32)
-            nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, Cdim, L, ctx.n_entries)
-            ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+            ws, nbytes = _hash_workspace(B, Cdim, L, g_emb)
             # the scatter reads level-major gradients (coalesced): what the SDF kernels wrote (two features per level),
             # otherwise both operands transposed in ONE launch
             if lm is not None:
@@ -520,7 +519,7 @@ class GridSdfFunction(torch.autograd.Function):
                           L, B, Cdim, A, 0, st)
             _lib.call('msdf_hash_node_scatter', _lib.ptr(g_lm[0]), _lib.ptr(g_lm[1]), 0, _lib.ptr(x01),
                       _lib.ptr(ctx.offsets), _lib.ptr(g_emb), B, Cdim, L, S, H, _lib.ptr(gg), ctx.n_entries,
-                      _lib.ptr(ws), int(nbytes), st)
+                      _lib.ptr(ws), nbytes, st)
             parallel.mark_grad_ready(g_emb)
             done.append(g_emb)
 
@@ -784,9 +783,13 @@ class LaplaceDensityFunction(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # hash grid (mirrors the reference's two autograd Functions, hashencoder/hashgrid.py:14-101)
 # ---------------------------------------------------------------------------
-# 'binned' (default): the embedding gradients are summed per table slice in LDS (msdf_hash_encode_*_ws, one record per
-# corner through a caller-owned workspace); 'atomic': one float atomic per corner like the reference's kernels
+# MSDF_HASH_SCATTER (this layer's switch alone; the library does not read it): 'binned' (default) -- the embedding
+# gradients are summed per table slice in LDS (msdf_hash_encode_*_ws, one record per corner through a caller-owned
+# workspace); 'atomic' -- one float atomic per corner like the reference's kernels, and the three-node path of the model
 HASH_SCATTER = _os.environ.get('MSDF_HASH_SCATTER', 'binned')
+if HASH_SCATTER not in ('binned', 'atomic'):
+    raise RuntimeError("monosdf_amd: MSDF_HASH_SCATTER must be 'binned' or 'atomic', got %r (the library's switch for "
+                       "the first binned form is MSDF_HASH_BINNED_FORM=1)" % HASH_SCATTER)
 
 
 def _hash_workspace(B, Cdim, L, embeddings):
@@ -794,25 +797,42 @@ def _hash_workspace(B, Cdim, L, embeddings):
     return torch.empty(int(n), device=embeddings.device, dtype=torch.uint8), int(n)
 
 
+def _hash_forward(inputs, embeddings, offsets, S, H, want_dy):
+    """msdf_hash_encode_forward.  Returns (features [B, L C], (inputs, embeddings, offsets, dy_dx) as the kernels read
+    them, dims); dy_dx is [B, L D C], or a one-column stand-in without want_dy."""
+    inputs = _need_cuda(inputs, 'inputs')
+    embeddings = _need_cuda(embeddings, 'embeddings')
+    offsets = offsets.contiguous()
+    if offsets.dtype != torch.int32 or not offsets.is_cuda:
+        raise RuntimeError('monosdf_amd: offsets must be a GPU int32 tensor')
+    B, D = inputs.shape
+    L, Cdim = offsets.shape[0] - 1, embeddings.shape[1]
+    outputs = torch.empty(L, B, Cdim, device=inputs.device, dtype=torch.float32)
+    dy_dx = torch.empty(B, L * D * Cdim if want_dy else 1, device=inputs.device, dtype=torch.float32)
+    _lib.call('msdf_hash_encode_forward', _lib.ptr(inputs), _lib.ptr(embeddings), _lib.ptr(offsets),
+              _lib.ptr(outputs), B, D, Cdim, L, float(S), int(H), int(bool(want_dy)), _lib.ptr(dy_dx), _lib.stream_ptr())
+    return (outputs.permute(1, 0, 2).reshape(B, L * Cdim), (inputs, embeddings, offsets, dy_dx),
+            (B, D, Cdim, L, float(S), int(H)))
+
+
+def _table_gradient(name, head, dims, tail, embeddings, binned):
+    """The reference-order gradient entry point name(*head, B, D, C, L, S, H, *tail, stream) -- tensors and ints -- or,
+    binned, its _ws form: the same arguments, then the table's rows and the scatter workspace."""
+    B, D, Cdim, L, S, H = dims
+    args = [_lib.ptr(t) for t in head] + [B, D, Cdim, L, S, H] + [a if isinstance(a, int) else _lib.ptr(a) for a in tail]
+    if binned:
+        ws, nbytes = _hash_workspace(B, Cdim, L, embeddings)
+        name, args = name + '_ws', args + [embeddings.shape[0], _lib.ptr(ws), nbytes]
+    _lib.call(name, *args, _lib.stream_ptr())
+
+
 class HashEncodeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, embeddings, offsets, S, H, calc_grad_inputs):
-        inputs = _need_cuda(inputs, 'inputs')
-        embeddings = _need_cuda(embeddings, 'embeddings')
-        offsets = offsets.contiguous()
-        if offsets.dtype != torch.int32 or not offsets.is_cuda:
-            raise RuntimeError('monosdf_amd: offsets must be a GPU int32 tensor')
-        B, D = inputs.shape
-        L, Cdim = offsets.shape[0] - 1, embeddings.shape[1]
-        outputs = torch.empty(L, B, Cdim, device=inputs.device, dtype=torch.float32)
-        dy_dx = torch.empty(B, L * D * Cdim if calc_grad_inputs else 1, device=inputs.device, dtype=torch.float32)
-        _lib.call('msdf_hash_encode_forward', _lib.ptr(inputs), _lib.ptr(embeddings), _lib.ptr(offsets),
-                  _lib.ptr(outputs), B, D, Cdim, L, float(S), int(H), int(bool(calc_grad_inputs)),
-                  _lib.ptr(dy_dx), _lib.stream_ptr())
-        ctx.save_for_backward(inputs, embeddings, offsets, dy_dx)
-        ctx.dims = (B, D, Cdim, L, float(S), int(H))
+        out, saved, ctx.dims = _hash_forward(inputs, embeddings, offsets, S, H, calc_grad_inputs)
+        ctx.save_for_backward(*saved)
         ctx.calc_grad_inputs = bool(calc_grad_inputs)
-        return outputs.permute(1, 0, 2).reshape(B, L * Cdim)
+        return out
 
     @staticmethod
     def backward(ctx, grad):
@@ -827,21 +847,13 @@ class HashEncodeFunction(torch.autograd.Function):
 class HashEncodeBackwardFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grad, inputs, embeddings, offsets, dy_dx, dims, calc_grad_inputs, want_emb=True):
-        B, D, Cdim, L, S, H = dims
         grad = _need_cuda(grad, 'grad')
         g_in = torch.zeros_like(inputs)
         # the reference always scatters into grad_embeddings, even when autograd discards it
         # (SURVEY 8a11); want_emb=False skips that wasted pass, the result the caller sees is identical
         g_emb = torch.zeros_like(embeddings) if want_emb else None
-        if want_emb and HASH_SCATTER == 'binned':
-            ws, nbytes = _hash_workspace(B, Cdim, L, embeddings)
-            _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings),
-                      _lib.ptr(offsets), _lib.ptr(g_emb), B, D, Cdim, L, S, H, int(calc_grad_inputs),
-                      _lib.ptr(dy_dx), _lib.ptr(g_in), embeddings.shape[0], _lib.ptr(ws), nbytes, _lib.stream_ptr())
-        else:
-            _lib.call('msdf_hash_encode_backward', _lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings),
-                      _lib.ptr(offsets), _lib.ptr(g_emb), B, D, Cdim, L, S, H, int(calc_grad_inputs),
-                      _lib.ptr(dy_dx), _lib.ptr(g_in), _lib.stream_ptr())
+        _table_gradient('msdf_hash_encode_backward', (grad, inputs, embeddings, offsets, g_emb), dims,
+                        (int(calc_grad_inputs), dy_dx, g_in), embeddings, want_emb and HASH_SCATTER == 'binned')
         if g_emb is None:
             g_emb = embeddings.new_zeros(1)
         ctx.save_for_backward(grad, inputs, embeddings, offsets, dy_dx)
@@ -853,20 +865,12 @@ class HashEncodeBackwardFunction(torch.autograd.Function):
     def backward(ctx, gg_in, gg_emb):
         # like the reference: gg_emb is ignored and nothing flows to the inputs (hashgrid.py:87,101)
         grad, inputs, embeddings, offsets, dy_dx = ctx.saved_tensors
-        B, D, Cdim, L, S, H = ctx.dims
         gg_in = _need_cuda(gg_in, 'grad_grad_inputs')
         grad_grad = torch.zeros_like(grad)
         grad2_emb = torch.zeros_like(embeddings)
-        if HASH_SCATTER == 'binned' and Cdim > 1:
-            ws, nbytes = _hash_workspace(B, Cdim, L, embeddings)
-            _lib.call('msdf_hash_encode_second_backward_ws', _lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings),
-                      _lib.ptr(offsets), B, D, Cdim, L, S, H, int(ctx.calc_grad_inputs), _lib.ptr(dy_dx),
-                      _lib.ptr(gg_in), _lib.ptr(grad_grad), _lib.ptr(grad2_emb), embeddings.shape[0], _lib.ptr(ws),
-                      nbytes, _lib.stream_ptr())
-        else:
-            _lib.call('msdf_hash_encode_second_backward', _lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(embeddings),
-                      _lib.ptr(offsets), B, D, Cdim, L, S, H, int(ctx.calc_grad_inputs), _lib.ptr(dy_dx),
-                      _lib.ptr(gg_in), _lib.ptr(grad_grad), _lib.ptr(grad2_emb), _lib.stream_ptr())
+        _table_gradient('msdf_hash_encode_second_backward', (grad, inputs, embeddings, offsets), ctx.dims,
+                        (int(ctx.calc_grad_inputs), dy_dx, gg_in, grad_grad, grad2_emb), embeddings,
+                        HASH_SCATTER == 'binned' and ctx.dims[2] > 1)
         return grad_grad, None, grad2_emb, None, None, None, None, None
 
 
@@ -875,18 +879,10 @@ class HashEncodeWithJacobian(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, embeddings, offsets, S, H):
-        inputs = _need_cuda(inputs, 'inputs')
-        embeddings_c = _need_cuda(embeddings, 'embeddings')
-        B, D = inputs.shape
-        L, Cdim = offsets.shape[0] - 1, embeddings.shape[1]
-        outputs = torch.empty(L, B, Cdim, device=inputs.device, dtype=torch.float32)
-        dy_dx = torch.empty(B, L * D * Cdim, device=inputs.device, dtype=torch.float32)
-        _lib.call('msdf_hash_encode_forward', _lib.ptr(inputs), _lib.ptr(embeddings_c), _lib.ptr(offsets),
-                  _lib.ptr(outputs), B, D, Cdim, L, float(S), int(H), 1, _lib.ptr(dy_dx), _lib.stream_ptr())
-        ctx.save_for_backward(inputs, embeddings_c, offsets, dy_dx)
-        ctx.dims = (B, D, Cdim, L, float(S), int(H))
-        ctx.mark_non_differentiable(dy_dx)
-        return outputs.permute(1, 0, 2).reshape(B, L * Cdim), dy_dx
+        out, saved, ctx.dims = _hash_forward(inputs, embeddings, offsets, S, H, True)
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(saved[3])
+        return out, saved[3]
 
     @staticmethod
     def backward(ctx, grad, _g_dy):

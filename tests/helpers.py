@@ -107,3 +107,35 @@ def check(errlog, test, case, key, err, default=TOL):
     if os.environ.get('MSDF_PARITY_MEASURE') == '1':
         return
     assert err <= tol, (test, case, key, err, tol)
+
+
+def hash_table_gradients(emb, offs, S, H, x, grad, grad2, gg, forms):
+    """The hash grid's table-gradient entry points through raw ctypes: the forward for dy_dx, then every form named in
+    `forms`, each into a fresh buffer (zeros; NaN for the "=" form 'fused_out'), returned by name.  'atomic' / 'ws':
+    msdf_hash_encode_backward / _ws of `grad` (also '<form>_inputs'); 'atomic_second' / 'ws_second': the second
+    backward of (`grad2`, gg) (also '<form>_grad'); 'fused' / 'fused_out': both terms.  Also 'dy_dx', 'workspace', 'nbytes'."""
+    from monosdf_amd import _lib
+    P, st = _lib.ptr, _lib.stream_ptr()
+    (L, B, C), n = grad.shape, emb.shape[0]
+    dy = torch.empty(B, L * 3 * C, device='cuda')
+    out = torch.empty(L, B, C, device='cuda')
+    _lib.call('msdf_hash_encode_forward', P(x), P(emb), P(offs), P(out), B, 3, C, L, S, H, 1, P(dy), st)
+    nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, C, L, n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+    r = {'dy_dx': dy, 'workspace': ws, 'nbytes': nbytes}
+    for f in forms:
+        t = r[f] = torch.full_like(emb, float('nan')) if f == 'fused_out' else torch.zeros_like(emb)
+        tail = (st,) if f.startswith('atomic') else (n, P(ws), nbytes, st)
+        sfx = '' if f.startswith('atomic') else '_ws'
+        if f in ('atomic', 'ws'):
+            gi = r[f + '_inputs'] = torch.zeros_like(x)
+            _lib.call('msdf_hash_encode_backward' + sfx, P(grad), P(x), P(emb), P(offs), P(t), B, 3, C, L, S, H, 1,
+                      P(dy), P(gi), *tail)
+        elif f in ('atomic_second', 'ws_second'):
+            ggrad = r[f + '_grad'] = torch.zeros(L, B, C, device='cuda')
+            _lib.call('msdf_hash_encode_second_backward' + sfx, P(grad2), P(x), P(emb), P(offs), B, 3, C, L, S, H, 1,
+                      P(dy), P(gg), P(ggrad), P(t), *tail)
+        else:
+            _lib.call('msdf_hash_encode_backward_' + f, P(grad), P(grad2), P(x), P(offs), P(t), B, 3, C, L, S, H,
+                      P(gg), *tail)
+    return r

@@ -170,7 +170,7 @@ def test_fullsize_binned_scatter_equals_atomic_scatter():
     """configs[2] size (104,448 points, 16 x 2, 2^19 entries per hashed level): the binned scatter (crowded bins are
     cut over several workgroups, the coarse levels hold hundreds of contributions per entry) against the
     one-atomic-per-corner kernels, first order, second order and both fused."""
-    from monosdf_amd import _lib
+    from helpers import hash_table_gradients
     from monosdf_amd.hashencoder.hashgrid import HashEncoder
     enc = HashEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
                       desired_resolution=2048).cuda()
@@ -184,28 +184,9 @@ def test_fullsize_binned_scatter_equals_atomic_scatter():
     grad2 = torch.randn(L, B, C, device='cuda', generator=g)
     gg = torch.randn(B, 3, device='cuda', generator=g)
     emb, offs = enc.embeddings.detach(), enc.offsets
-    n = emb.shape[0]
-    S, H = enc.log2_scale, int(enc.base_resolution)
-    st = _lib.stream_ptr()
-    dy = torch.empty(B, L * 3 * C, device='cuda')
-    out = torch.empty(L, B, C, device='cuda')
-    _lib.call('msdf_hash_encode_forward', _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(out), B, 3, C, L, S, H, 1,
-              _lib.ptr(dy), st)
-    a1, a2 = torch.zeros_like(emb), torch.zeros_like(emb)
-    gi, ggrad = torch.zeros_like(x), torch.zeros(L, B, C, device='cuda')
-    _lib.call('msdf_hash_encode_backward', _lib.ptr(grad), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(a1),
-              B, 3, C, L, S, H, 0, _lib.ptr(dy), _lib.ptr(gi), st)
-    _lib.call('msdf_hash_encode_second_backward', _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), B, 3, C, L,
-              S, H, 1, _lib.ptr(dy), _lib.ptr(gg), _lib.ptr(ggrad), _lib.ptr(a2), st)
-    nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, C, L, n)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
-    b1, b2, bf = torch.zeros_like(emb), torch.zeros_like(emb), torch.zeros_like(emb)
-    _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(b1),
-              B, 3, C, L, S, H, 0, _lib.ptr(dy), None, n, _lib.ptr(ws), nbytes, st)
-    _lib.call('msdf_hash_encode_second_backward_ws', _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), B, 3, C,
-              L, S, H, 1, _lib.ptr(dy), _lib.ptr(gg), None, _lib.ptr(b2), n, _lib.ptr(ws), nbytes, st)
-    _lib.call('msdf_hash_encode_backward_fused', _lib.ptr(grad), _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(offs), _lib.ptr(bf),
-              B, 3, C, L, S, H, _lib.ptr(gg), n, _lib.ptr(ws), nbytes, st)
+    r = hash_table_gradients(emb, offs, enc.log2_scale, int(enc.base_resolution), x, grad, grad2, gg,
+                             ('atomic', 'atomic_second', 'ws', 'ws_second', 'fused'))
+    a1, a2, b1, b2, bf = r['atomic'], r['atomic_second'], r['ws'], r['ws_second'], r['fused']
     rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()
     assert a1.abs().max().item() > 0 and a2.abs().max().item() > 0
     # both sides sum thousands of signed fp32 terms per crowded entry in an arbitrary order: 1e-4 of the largest entry
@@ -221,7 +202,7 @@ def test_fullsize_scatter_of_ray_ordered_samples_and_output_form():
     (runs inside 16-lane rows).  Ray-ordered samples 2e-4 apart give runs of every length on every level, some points
     outside [0, 1] (no contribution) break them; against the one-atomic-per-corner kernels.  And the "=" form
     (msdf_hash_encode_backward_fused_out) into an uninitialised buffer equals the "+=" form into zeros."""
-    from monosdf_amd import _lib
+    from helpers import hash_table_gradients
     from monosdf_amd.hashencoder.hashgrid import HashEncoder
     enc = HashEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
                       desired_resolution=2048).cuda()
@@ -242,29 +223,9 @@ def test_fullsize_scatter_of_ray_ordered_samples_and_output_form():
     grad2 = torch.randn(L, B, C, device='cuda', generator=g)
     gg = torch.randn(B, 3, device='cuda', generator=g)
     emb, offs = enc.embeddings.detach(), enc.offsets
-    n = emb.shape[0]
-    S, H = enc.log2_scale, int(enc.base_resolution)
-    st = _lib.stream_ptr()
-    dy = torch.empty(B, L * 3 * C, device='cuda')
-    out = torch.empty(L, B, C, device='cuda')
-    _lib.call('msdf_hash_encode_forward', _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(out), B, 3, C, L, S, H, 1,
-              _lib.ptr(dy), st)
-    a1, a2 = torch.zeros_like(emb), torch.zeros_like(emb)
-    gi, ggrad = torch.zeros_like(x), torch.zeros(L, B, C, device='cuda')
-    _lib.call('msdf_hash_encode_backward', _lib.ptr(grad), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(a1),
-              B, 3, C, L, S, H, 0, _lib.ptr(dy), _lib.ptr(gi), st)
-    _lib.call('msdf_hash_encode_second_backward', _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), B, 3, C, L,
-              S, H, 1, _lib.ptr(dy), _lib.ptr(gg), _lib.ptr(ggrad), _lib.ptr(a2), st)
-    nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, C, L, n)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
-    b1, bf = torch.zeros_like(emb), torch.zeros_like(emb)
-    bo = torch.full_like(emb, float('nan'))
-    _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad), _lib.ptr(x), _lib.ptr(emb), _lib.ptr(offs), _lib.ptr(b1),
-              B, 3, C, L, S, H, 0, _lib.ptr(dy), None, n, _lib.ptr(ws), nbytes, st)
-    _lib.call('msdf_hash_encode_backward_fused', _lib.ptr(grad), _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(offs), _lib.ptr(bf),
-              B, 3, C, L, S, H, _lib.ptr(gg), n, _lib.ptr(ws), nbytes, st)
-    _lib.call('msdf_hash_encode_backward_fused_out', _lib.ptr(grad), _lib.ptr(grad2), _lib.ptr(x), _lib.ptr(offs),
-              _lib.ptr(bo), B, 3, C, L, S, H, _lib.ptr(gg), n, _lib.ptr(ws), nbytes, st)
+    r = hash_table_gradients(emb, offs, enc.log2_scale, int(enc.base_resolution), x, grad, grad2, gg,
+                             ('atomic', 'atomic_second', 'ws', 'fused', 'fused_out'))
+    a1, a2, b1, bf, bo = r['atomic'], r['atomic_second'], r['ws'], r['fused'], r['fused_out']
     rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()
     assert rel(b1, a1) < 1e-4, rel(b1, a1)
     assert rel(bf, a1 + a2) < 1e-4, rel(bf, a1 + a2)
@@ -382,10 +343,10 @@ def test_fullsize_sdf_volume_512():
 
 def test_first_form_of_the_binned_scatter_still_runs():
     """The count / scan / place / accumulate form stays in the library as the path for tables of more than 8,192 slices
-    per level; MSDF_HASH_SCATTER=1 (read once per process) selects it: the ray-ordered scatter test in a child process."""
+    per level; MSDF_HASH_BINNED_FORM=1 (read once per process) selects it: the ray-ordered scatter test in a child process."""
     import subprocess
     import sys
-    env = dict(os.environ, MSDF_HASH_SCATTER='1')
+    env = dict(os.environ, MSDF_HASH_BINNED_FORM='1')
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', os.path.abspath(__file__), '-k',
                         'ray_ordered or binned_scatter_equals'], cwd=root, env=env, capture_output=True, text=True,

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ALL_CASES, Case, check, digest, rel_err
+from helpers import ALL_CASES, Case, check, digest, hash_table_gradients, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -228,32 +228,19 @@ def test_hash_encoder_kernels():
         grad_g = grad.cuda()           # keep device tensors alive until the kernels have been enqueued
         ge_o = hg.encode_backward_grid(grad, x, geo, geo['n_entries'])
         gi_o = hg.encode_backward_input(grad, dy_o, geo)
-        ge, gi = torch.zeros_like(eg), torch.zeros_like(xg)
-        _lib.call('msdf_hash_encode_backward', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg), _lib.ptr(offs),
-                  _lib.ptr(ge), B, 3, C, L, geo['S'], geo['H'], 1, _lib.ptr(dy), _lib.ptr(gi), st)
-        assert rel_err(ge, ge_o) < 1e-5 and rel_err(gi, gi_o) < 1e-5
         ggi = torch.randn(B, 3, generator=g)
         ggi_g = ggi.cuda()
+        # atomic, and the same sums through the binned scatter (per-slice LDS accumulation instead of one atomic per corner)
+        r = hash_table_gradients(eg, offs, geo['S'], geo['H'], xg, grad_g, grad_g, ggi_g,
+                                 ('atomic', 'atomic_second', 'ws', 'ws_second'))
+        ge, gi, gg, g2 = r['atomic'], r['atomic_inputs'], r['atomic_second_grad'], r['atomic_second']
+        ge_b, gi_b, gg_b, g2_b = r['ws'], r['ws_inputs'], r['ws_second_grad'], r['ws_second']
+        n_entries, ws, nbytes = geo['n_entries'], r['workspace'], r['nbytes']
+        assert rel_err(ge, ge_o) < 1e-5 and rel_err(gi, gi_o) < 1e-5
         gg_o = hg.second_backward_grad(ggi, dy_o, geo)
         g2_o = hg.second_backward_embedding(grad, x, ggi, geo, geo['n_entries'])
-        gg, g2 = torch.zeros(L, B, C, device='cuda'), torch.zeros_like(eg)
-        _lib.call('msdf_hash_encode_second_backward', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg),
-                  _lib.ptr(offs), B, 3, C, L, geo['S'], geo['H'], 1, _lib.ptr(dy), _lib.ptr(ggi_g),
-                  _lib.ptr(gg), _lib.ptr(g2), st)
         assert rel_err(gg, gg_o) < 1e-5 and rel_err(g2, g2_o) < 1e-5
-        # the same sums through the binned scatter (per-slice LDS accumulation instead of one atomic per corner) ...
-        n_entries = geo['n_entries']
-        nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, C, L, n_entries)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
-        ge_b, gi_b = torch.zeros_like(eg), torch.zeros_like(xg)
-        _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg), _lib.ptr(offs),
-                  _lib.ptr(ge_b), B, 3, C, L, geo['S'], geo['H'], 1, _lib.ptr(dy), _lib.ptr(gi_b), n_entries,
-                  _lib.ptr(ws), nbytes, st)
         assert rel_err(ge_b, ge_o) < 1e-5 and rel_err(gi_b, gi_o) < 1e-5
-        gg_b, g2_b = torch.zeros(L, B, C, device='cuda'), torch.zeros_like(eg)
-        _lib.call('msdf_hash_encode_second_backward_ws', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg),
-                  _lib.ptr(offs), B, 3, C, L, geo['S'], geo['H'], 1, _lib.ptr(dy), _lib.ptr(ggi_g), _lib.ptr(gg_b),
-                  _lib.ptr(g2_b), n_entries, _lib.ptr(ws), nbytes, st)
         assert rel_err(gg_b, gg_o) < 1e-5 and rel_err(g2_b, g2_o) < 1e-5
         # ... accumulating into a table that already holds values (the reference's kernels ADD, hashgrid.py:75-76)
         _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg), _lib.ptr(offs),
@@ -263,9 +250,7 @@ def test_hash_encoder_kernels():
         # ... and both gradients in ONE scatter
         grad2 = torch.randn(L, B, C, generator=g)
         grad2_g = grad2.cuda()
-        fused = torch.zeros_like(eg)
-        _lib.call('msdf_hash_encode_backward_fused', _lib.ptr(grad_g), _lib.ptr(grad2_g), _lib.ptr(xg), _lib.ptr(offs),
-                  _lib.ptr(fused), B, 3, C, L, geo['S'], geo['H'], _lib.ptr(ggi_g), n_entries, _lib.ptr(ws), nbytes, st)
+        fused = hash_table_gradients(eg, offs, geo['S'], geo['H'], xg, grad_g, grad2_g, ggi_g, ('fused',))['fused']
         want = ge_o + hg.second_backward_embedding(grad2, x, ggi, geo, geo['n_entries'])
         assert rel_err(fused, want) < 1e-5
         # calc_grad_inputs = 2: dy_dx level-major [L, B, 3 C] in all three entry points, same numbers
@@ -395,6 +380,89 @@ def test_hash_encoder_single_feature_levels():
     _lib.call('msdf_hash_encode_backward_ws', _lib.ptr(grad_g), _lib.ptr(xg), _lib.ptr(eg), _lib.ptr(offs),
               _lib.ptr(ge_b), B, 3, C, L, geo['S'], geo['H'], 0, _lib.ptr(dy), None, n_entries, _lib.ptr(ws), nbytes, st)
     assert rel_err(ge_b, ge_o) < 1e-5
+
+
+def test_hash_table_gradient_return_codes():
+    """The return-code table of include/monosdf_hip.h (hash-grid block) against the seven table-gradient entry points:
+    every refusal gives its documented code, in the documented order, and leaves grad_embeddings (a sentinel) untouched;
+    B == 0 leaves the "+=" forms' table alone and zeroes the "=" forms'.  Host-side returns and a memset only: every
+    buffer is nevertheless a valid operand of its call (B = 1,061: two place workgroups, the second partial)."""
+    import ctypes
+    from monosdf_amd import _lib
+    from monosdf_amd.hashencoder.hashgrid import HashEncoder
+    enc = HashEncoder(input_dim=3, num_levels=4, level_dim=2, base_resolution=4, log2_hashmap_size=13,
+                      desired_resolution=64).cuda()
+    B, L, C = 1061, 4, 2
+    OK, ARG, UNSUPPORTED = 0, 1, 3
+    g = torch.Generator(device='cuda').manual_seed(31)
+    x = torch.rand(B, 3, device='cuda', generator=g)
+    grad, grad2 = torch.randn(2, L, B, C, device='cuda', generator=g)
+    gg = torch.randn(B, 3, device='cuda', generator=g)
+    offs, n = enc.offsets, enc.embeddings.shape[0]
+    S, H = enc.log2_scale, int(enc.base_resolution)
+    lib, st = _lib.load(), _lib.stream_ptr()
+    nbytes = lib.msdf_hash_scatter_workspace_bytes(B, C, L, n)
+    base = dict(grad=grad, grad2=grad2, x=x, offs=offs, table=torch.full((n, C), 7.0, device='cuda'), gg=gg,
+                dy=torch.zeros(B, L * 3 * C, device='cuda'), gi=torch.zeros(B, 3, device='cuda'),
+                ggrad=torch.zeros(L, B, C, device='cuda'), ws=torch.empty(nbytes, dtype=torch.uint8, device='cuda'),
+                B=B, D=3, C=C, pitch=0, n=n, nbytes=nbytes)
+    FIRST = ('msdf_hash_encode_backward', 'msdf_hash_encode_backward_ws')
+    SECOND = ('msdf_hash_encode_second_backward', 'msdf_hash_encode_second_backward_ws')
+    FUSED = ('msdf_hash_encode_backward_fused', 'msdf_hash_encode_backward_fused_out')
+    NODE = 'msdf_hash_node_scatter'
+    ALL = FIRST + SECOND + FUSED + (NODE,)
+    BINNED = (FIRST[1], SECOND[1]) + FUSED + (NODE,)
+
+    def status(name, **kw):
+        a = dict(base, **kw)
+        p = lambda k: ctypes.c_void_p(a[k]) if isinstance(a[k], int) else _lib.ptr(a[k])      # None -> NULL
+        dims = (a['B'], a['D'], a['C'], L, S, H)
+        if name in FIRST:
+            args = (p('grad'), p('x'), None, p('offs'), p('table')) + dims + (1, p('dy'), p('gi'))
+        elif name in SECOND:
+            args = (p('grad2'), p('x'), None, p('offs')) + dims + (1, p('dy'), p('gg'), p('ggrad'), p('table'))
+        elif name in FUSED:
+            args = (p('grad'), p('grad2'), p('x'), p('offs'), p('table')) + dims + (p('gg'),)
+        else:
+            args = (p('grad'), p('grad2'), a['pitch'], p('x'), p('offs'), p('table'), a['B'], a['C'], L, S, H, p('gg'))
+        if name in BINNED:
+            args += (a['n'], p('ws'), a['nbytes'])
+        return getattr(lib, name)(*args, st)
+
+    def refused(names, code, **kw):
+        for name in names:
+            assert status(name, **kw) == code, (name, kw.keys(), code)
+
+    # 1, 2: D and C, before any pointer is looked at
+    refused(FIRST + SECOND + FUSED, UNSUPPORTED, D=2, table=None)
+    refused(ALL, UNSUPPORTED, C=3, table=None)
+    refused(SECOND + FUSED + (NODE,), UNSUPPORTED, C=1, B=0)
+    # 3: the always-required pointers, before B == 0
+    for k in ('table', 'grad', 'grad2', 'gg'):
+        refused(FUSED, ARG, B=0, **{k: None})
+    refused((NODE,), ARG, B=0, table=None)
+    # 4: no points -- "+=" forms leave the table alone, with every other pointer NULL where the contract allows it
+    none = dict(grad=None, grad2=None, x=None, offs=None, gg=None, dy=None, gi=None, ggrad=None, ws=None, nbytes=0)
+    refused(FIRST + SECOND, OK, B=0, **none)
+    refused(FUSED[:1], OK, B=0, x=None, offs=None, ws=None, nbytes=0)
+    # 5: a NULL operand of a requested output; the pitch of point-major rows
+    for names, k in ((FIRST, 'grad'), (FIRST, 'x'), (FIRST, 'offs'), (FIRST, 'dy'), (FIRST, 'gi'), (SECOND, 'grad2'),
+                     (SECOND, 'x'), (SECOND, 'offs'), (SECOND, 'gg'), (SECOND, 'dy'), (FUSED, 'x'), (FUSED, 'offs'),
+                     ((NODE,), 'grad'), ((NODE,), 'grad2'), ((NODE,), 'gg'), ((NODE,), 'x'), ((NODE,), 'offs')):
+        refused(names, ARG, **{k: None})
+    refused((NODE,), ARG, pitch=L * C - 1)
+    # 6: 2^31 floats of table, 2^31 corner records -- before the workspace is looked at
+    refused(BINNED, UNSUPPORTED, n=2 ** 30, ws=None)
+    refused(BINNED, UNSUPPORTED, B=2 ** 26, ws=None)
+    # 7: the workspace
+    refused(BINNED, ARG, ws=None)
+    refused(BINNED, ARG, nbytes=nbytes - 1)
+    refused(BINNED, ARG, ws=base['ws'].data_ptr() + 4)
+    assert torch.equal(base['table'], torch.full((n, C), 7.0, device='cuda'))
+    # 4 again, the "=" forms: an all-zero table (the node form with the NULL operands of empty tensors)
+    for name, kw in ((FUSED[1], {}), (NODE, none)):
+        table = torch.full((n, C), 7.0, device='cuda')
+        assert status(name, B=0, table=table, **kw) == OK and not table.any(), name
 
 
 @pytest.mark.parametrize('name', [n for n in ALL_CASES if 'eval' in n and 'image' not in n])
