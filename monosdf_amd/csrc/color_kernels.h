@@ -4,10 +4,11 @@
 
 typedef msdf_color_fwd_args_t ColorFwdArgs;
 
+template <class Core>
 __device__ __forceinline__ int wave_point(int& q) {
   const int lane = lane_id();
   q = lane >> 4;
-  return blockIdx.x * MLP_PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane & 15);
+  return blockIdx.x * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane & 15);
 }
 
 // misc block in slot layout: idr: [x(3) | PE(v) | n(3)], nerf: [PE(v)]; then code tiles
@@ -48,11 +49,6 @@ __device__ __forceinline__ void color_misc_tiles(v4f (&m)[5], const msdf_plan_t&
     for (int t = 0; t < 2; ++t)
       if (t < plan.aux_tiles) m[3 + t] = *(const v4f*)(code + (size_t)ray * aw + 16 * t + 4 * q);
   }
-}
-
-__device__ __forceinline__ void load_bias_c(v4f (&acc)[MT], const float* __restrict__ b, const int ot, const int q) {
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = (t < ot) ? *(const v4f*)(b + 16 * t + 4 * q) : V4ZERO;
 }
 
 
@@ -129,7 +125,7 @@ template <class Core>
 __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, const ColorFwdArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
   int q;
-  const int pt = wave_point(q);
+  const int pt = wave_point<Core>(q);
   const bool valid = pt < a.P;
   const int ptc = valid ? pt : a.P - 1;
   const int ray = ptc / a.spr;
@@ -145,7 +141,7 @@ __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, cons
   if constexpr (Core::BIAS_IN_HOOKS) {
     Core::gemm_bias(U0.ktp, acc, in, U0.ot, (const wvec*)a.wpack + U0.wf_off, lds, NoHooks(), a.bpack + U0.bias_off + 4 * q);
   } else {
-    load_bias_c(acc, a.bpack + U0.bias_off, U0.ot, q);
+    load_bias(acc, a.bpack + U0.bias_off, U0.ot, q);
     Core::gemm(U0.ktp, acc, in, U0.ot, (const wvec*)a.wpack + U0.wf_off, lds, NoHooks());
   }
   // ---- first layer, misc part (same accumulators)
@@ -180,7 +176,7 @@ __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, cons
       Core::gemm_bias(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, next_hooks(u + 1),
                       a.bpack + L.bias_off + 4 * q);
     } else {
-      load_bias_c(acc, a.bpack + L.bias_off, L.ot, q);
+      load_bias(acc, a.bpack + L.bias_off, L.ot, q);
       Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, next_hooks(u + 1));
     }
   }
@@ -220,7 +216,7 @@ template <class Core>
 __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, const ColorBwdArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
   int q;
-  const int pt = wave_point(q);
+  const int pt = wave_point<Core>(q);
   const bool valid = pt < a.P;
   const size_t Pp = (size_t)a.P_pad;
   const int nu = plan.n_layers;

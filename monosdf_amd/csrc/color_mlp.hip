@@ -8,45 +8,45 @@
 //
 // The plan's "layers" are pack units: unit 0 = first layer, feature columns;
 // unit 1 = first layer, misc columns; units 2.. = the remaining layers.
-#include "color_kernels.h"
+#include "mlp_launch.h"
 
-__global__ void __launch_bounds__(MLP_THREADS, MLP_WGS_PER_CU)
+__global__ void __launch_bounds__(CoreF32::THREADS, CoreF32::WGS_PER_CU)
 msdf_color_forward_k(const msdf_plan_t plan, const ColorFwdArgs a) {
   extern __shared__ v4f lds[];
   color_forward_body<CoreF32>(plan, a, lds);
 }
 
-__global__ void __launch_bounds__(MLP_THREADS, MLP_WGS_PER_CU)
+__global__ void __launch_bounds__(CoreF32::THREADS, CoreF32::WGS_PER_CU)
 msdf_color_backward_k(const msdf_plan_t plan, const ColorBwdArgs a) {
   extern __shared__ v4f lds[];
   color_backward_body<CoreF32>(plan, a, lds);
 }
 
-// bf16x3 launchers (color_mlp_b16.hip)
-int msdf_b16_color_forward(const msdf_plan_t*, const msdf_color_fwd_args_t*, hipStream_t);
-int msdf_b16_color_backward(const msdf_plan_t*, const msdf_color_bwd_args_t*, hipStream_t);
+// the kernels of a core
+static auto forward_kernel(CoreF32) { return msdf_color_forward_k; }
+static auto backward_kernel(CoreF32) { return msdf_color_backward_k; }
+template <int NS> static auto forward_kernel(CoreB16N<NS>) { return msdf_color_forward_b16_k<NS>; }
+template <int NS> static auto backward_kernel(CoreB16N<NS>) { return msdf_color_backward_b16_k<NS>; }
 
-static int color_prepare(const void* fn) {
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_BYTES) == hipSuccess
-             ? MSDF_OK : MSDF_ERR_LAUNCH;
-}
+// P_pad: whole workgroups (64 points on every core) that cover the P points
+static bool padded_ok(const int P, const int P_pad) { return P_pad >= P && (P_pad % CoreF32::PTS_PER_WG) == 0; }
 
 extern "C" int msdf_color_forward(const msdf_plan_t* plan, const msdf_color_fwd_args_t* a, void* stream) {
   if (plan == nullptr || a == nullptr || a->P < 0 || a->spr < 1) return MSDF_ERR_ARG;
   if (a->P == 0) return MSDF_OK;
-  if (a->P_pad < a->P || (a->P_pad % MLP_PTS_PER_WG) != 0) return MSDF_ERR_ARG;
-  if (plan->precision == MSDF_PRECISION_BF16X3 || plan->precision == MSDF_PRECISION_BF16X6) return msdf_b16_color_forward(plan, a, (hipStream_t)stream);
-  if (color_prepare((const void*)msdf_color_forward_k)) return MSDF_ERR_LAUNCH;
-  msdf_color_forward_k<<<a->P_pad / MLP_PTS_PER_WG, MLP_THREADS, MLP_LDS_BYTES, (hipStream_t)stream>>>(*plan, *a);
-  return msdf_check_launch();
+  if (!padded_ok(a->P, a->P_pad)) return MSDF_ERR_ARG;
+  return mlp_with_core(plan, [&](auto core) {
+    typedef decltype(core) Core;
+    return mlp_launch<Core>(forward_kernel(core), a->P_pad / Core::PTS_PER_WG, stream, *plan, *a);
+  });
 }
 
 extern "C" int msdf_color_backward(const msdf_plan_t* plan, const msdf_color_bwd_args_t* a, void* stream) {
   if (plan == nullptr || a == nullptr || a->P < 0) return MSDF_ERR_ARG;
   if (a->P == 0) return MSDF_OK;
-  if (a->P_pad < a->P || (a->P_pad % MLP_PTS_PER_WG) != 0) return MSDF_ERR_ARG;
-  if (plan->precision == MSDF_PRECISION_BF16X3 || plan->precision == MSDF_PRECISION_BF16X6) return msdf_b16_color_backward(plan, a, (hipStream_t)stream);
-  if (color_prepare((const void*)msdf_color_backward_k)) return MSDF_ERR_LAUNCH;
-  msdf_color_backward_k<<<a->P_pad / MLP_PTS_PER_WG, MLP_THREADS, MLP_LDS_BYTES, (hipStream_t)stream>>>(*plan, *a);
-  return msdf_check_launch();
+  if (!padded_ok(a->P, a->P_pad)) return MSDF_ERR_ARG;
+  return mlp_with_core(plan, [&](auto core) {
+    typedef decltype(core) Core;
+    return mlp_launch<Core>(backward_kernel(core), a->P_pad / Core::PTS_PER_WG, stream, *plan, *a);
+  });
 }

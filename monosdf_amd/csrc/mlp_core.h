@@ -24,13 +24,9 @@
                                          // built and tested with 4; 8 was a timing experiment of the fp32 kernels only
                                          // (slower) and is not a supported configuration
 #endif
-#define MLP_THREADS (64 * MLP_WAVES)
 #define MLP_PTS_PER_WAVE 16
-#define MLP_PTS_PER_WG (16 * MLP_WAVES)
-#define MLP_WGS_PER_CU (8 / MLP_WAVES)   // 256 registers per lane: two waves per SIMD
 #define CHUNK_OT 2                       // out tiles per LDS chunk
 #define LDS_BUF_F4 (CHUNK_OT * MT * 64)  // float4 per LDS buffer (34 KB)
-#define MLP_LDS_BYTES (2 * LDS_BUF_F4 * 16)
 
 #define V4ZERO ((v4f){0.f, 0.f, 0.f, 0.f})
 
@@ -40,6 +36,19 @@ __device__ __forceinline__ v4f mfma4(const v4f a, const v4f b, v4f c) {
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
   return c;
+}
+
+// The same for a pair of out tiles that share the B operand, the two chains interleaved (c0, c1, c0, c1 ...): each matrix
+// instruction then has an independent one between it and the next of its own chain.
+__device__ __forceinline__ void mfma4_pair(const v4f a0, const v4f a1, const v4f b, v4f& c0, v4f& c1) {
+  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.x, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.y, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b.z, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b.z, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b.w, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b.w, c1, 0, 0, 0);
 }
 
 // Copy one weight chunk (n_f4 float4, a multiple of 64) global -> LDS with LDS-DMA, linear image.
@@ -107,6 +116,13 @@ struct BiasHooks {
   __device__ __forceinline__ void drain() { inner.drain(); }
 };
 
+// The other order (a core without BIAS_IN_HOOKS): the accumulators start from the bias.  b: the packed bias row, q: the
+// lane's quarter.
+__device__ __forceinline__ void load_bias(v4f (&acc)[MT], const float* __restrict__ b, const int ot, const int q) {
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = (t < ot) ? *(const v4f*)(b + 16 * t + 4 * q) : V4ZERO;
+}
+
 // PPC = pairs of out tiles per weight chunk: 1 for the wide products; narrow ones (K = 3, 5 tiles: the network
 // input layers, the misc block of the colour network) take several pairs per chunk -- a pair is then only 24 / 40
 // matrix instructions, too little work between two barriers.
@@ -159,15 +175,7 @@ __device__ __forceinline__ void gemm_tiles(v4f (&acc)[MT], const v4f (&in)[MT], 
               n1 = w1[(kt + 1) * 64];
             }
             __builtin_amdgcn_sched_barrier(0);   // keep the prefetch above the MFMAs
-            const v4f b = in[kt];
-            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.x, c1, 0, 0, 0);
-            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.y, c1, 0, 0, 0);
-            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b.z, c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b.z, c1, 0, 0, 0);
-            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b.w, c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b.w, c1, 0, 0, 0);
+            mfma4_pair(a0, a1, in[kt], c0, c1);
             a0 = n0;
             a1 = n1;
           }
@@ -177,20 +185,7 @@ __device__ __forceinline__ void gemm_tiles(v4f (&acc)[MT], const v4f (&in)[MT], 
 #pragma unroll
           for (int kt = 0; kt < KMAX; ++kt) {
             if (kt < K) {
-              const v4f a0 = w0[kt * 64];
-              const v4f a1 = w1[kt * 64];
-              const v4f b = in[kt];
-              v4f c0 = acc[o0], c1 = acc[o1];
-              c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, c0, 0, 0, 0);
-              c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.x, c1, 0, 0, 0);
-              c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, c0, 0, 0, 0);
-              c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.y, c1, 0, 0, 0);
-              c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b.z, c0, 0, 0, 0);
-              c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b.z, c1, 0, 0, 0);
-              c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b.w, c0, 0, 0, 0);
-              c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b.w, c1, 0, 0, 0);
-              acc[o0] = c0;
-              acc[o1] = c1;
+              mfma4_pair(w0[kt * 64], w1[kt * 64], in[kt], acc[o0], acc[o1]);
             }
           }
         }
@@ -356,6 +351,11 @@ __device__ __forceinline__ void pe_jacobian(v4f (&rbar)[5], const float x0, cons
 // ---------------------------------------------------------------------------
 struct CoreF32 {
   typedef v4f wvec;                                  // one 16-byte element of the weight pack
+  // how a kernel of this core is launched (mlp_launch.h); MLP_WAVES is the one knob
+  static constexpr int THREADS = 64 * MLP_WAVES;
+  static constexpr int PTS_PER_WG = MLP_PTS_PER_WAVE * MLP_WAVES;
+  static constexpr int WGS_PER_CU = 8 / MLP_WAVES;   // 256 registers per lane: two waves per SIMD
+  static constexpr int LDS_BYTES = 2 * LDS_BUF_F4 * 16;
   // the products that carry a bias add it to the finished tiles (BiasHooks) instead of starting the accumulators from
   // it: the forward + gradient kernel spilled 208 bytes per lane with 17 bias tiles live beside two activation vectors,
   // 36 now (2.155 -> 2.08 ms, same box), the colour forward kernel 0.339 -> 0.332 ms
@@ -385,3 +385,28 @@ struct CoreF32 {
     gemm_dispatch(kp, acc, in, OT, wsrc, (v4f*)lds, bh);
   }
 };
+
+// ---------------------------------------------------------------------------
+// The fp32 part of a weight pack, the same for every core (third grid plane of the pack kernels, sdf_mlp.hip /
+// sdf_mlp_b16.hip): the layer's bias row in out-slot order and, behind the last layer, the plan's dot-product rows
+// (the sdf row / the three colour rows) in in-slot order.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void pack_bias_rows(const msdf_plan_t& plan, const int l, const msdf_packrule_t& R,
+                                               const int* __restrict__ rowmap, const int* __restrict__ colmap,
+                                               const float* __restrict__ W, const float* __restrict__ flat_b,
+                                               float* __restrict__ bpack, const int t0, const int stride) {
+  const msdf_layer_t L = plan.layer[l];
+  for (int i = t0; i < 16 * L.ot; i += stride) {
+    const int row = rowmap[i];
+    bpack[L.bias_off + i] = (row >= 0) ? flat_b[R.b_off + row] : 0.f;
+  }
+  if (l == plan.n_layers - 1 && plan.wsdf_off >= 0) {
+    for (int rr = 0; rr < plan.out_rows; ++rr) {
+      const int row = rowmap[plan.sdf_slot + rr];
+      for (int i = t0; i < 16 * L.kt; i += stride) {
+        const int col = colmap[i];
+        bpack[plan.wsdf_off + rr * 16 * L.kt + i] = (col >= 0 && row >= 0) ? R.scale * W[(size_t)row * R.cols + col] : 0.f;
+      }
+    }
+  }
+}

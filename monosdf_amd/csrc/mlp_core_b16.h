@@ -42,8 +42,6 @@ __device__ __forceinline__ float softplus100_lean(const float a) {
 // load/store-heavy epilogue overlaps the other's matrix products.  (8 waves sharing 4-tile chunks -- half the
 // L2 -> LDS traffic -- measured the same on the forward kernel: the weight stream is not what bounds it, see DESIGN.md.)
 #define B16_WAVES 4
-#define B16_THREADS (64 * B16_WAVES)
-#define B16_PTS_PER_WG (16 * B16_WAVES)
 
 // NS planes per operand.  An LDS weight chunk holds CH out tiles: two with two planes (36 KB per buffer), one with three
 // (27 KB) -- either way two workgroups fit a CU and a chunk is 54 matrix instructions at K = 288.
@@ -52,7 +50,6 @@ struct B16Cfg {
   static_assert(NS == 2 || NS == 3, "two planes (bf16x3) or three (bf16x6)");
   static constexpr int CH = (NS == 2) ? 2 : 1;
   static constexpr int BUF_V8 = CH * KB_MAX * NS * 64;      // v8bf (16 B) per LDS buffer
-  static constexpr int LDS_BYTES = 2 * BUF_V8 * 16;         // 72 KB / 54 KB: two workgroups per CU
   static constexpr int RING = (NS == 2) ? 3 : 2;            // fragment sets in flight (NS * RING * 4 registers; 3 x 3 spills: 7.7 -> 8.2 ms)
 };
 
@@ -153,7 +150,7 @@ __device__ __forceinline__ v4f b16_tile_dyn(v4f c, const v8bf* __restrict__ w, c
 // The product's hooks (mlp_core.h, NoHooks) are called per PAIR of out tiles: pre() after the barrier that opens the
 // pair's (first) chunk, post() after its last MFMA -- the activation's VALU work and the epilogue's memory traffic
 // overlap the other wave's MFMAs instead of forming a phase of their own.
-// All B16_THREADS threads of the workgroup call this together (barriers inside).
+// All threads of the workgroup call this together (barriers inside).
 template <int NS, int KB_T, class Hooks>
 __device__ __forceinline__ void gemm_b16(v4f (&acc)[MT], const B16Act<NS>& act, const int OT, const int kb_rt,
                                          const v8bf* __restrict__ wsrc, v8bf* lds, Hooks& hk) {
@@ -255,6 +252,11 @@ template <int NS>
 struct CoreB16N {
   typedef v8bf wvec;
   static constexpr int PLANES = NS;
+  // how a kernel of this core is launched (mlp_launch.h)
+  static constexpr int THREADS = 64 * B16_WAVES;
+  static constexpr int PTS_PER_WG = MLP_PTS_PER_WAVE * B16_WAVES;
+  static constexpr int WGS_PER_CU = 2;
+  static constexpr int LDS_BYTES = 2 * B16Cfg<NS>::BUF_V8 * 16;      // two buffers: 72 KB / 54 KB, two workgroups per CU
   // three planes only: the two-plane core keeps its accumulators starting from the bias (its results, and the rows of
   // the tolerance table measured on them, stay as they are; it gains 1 % from the change, the three-plane core 10 %)
   static constexpr bool BIAS_IN_HOOKS = (NS == 3);

@@ -15,11 +15,12 @@ struct PointCtx {
   float x0, x1, x2;
 };
 
+template <class Core>
 __device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, const int P) {
   PointCtx c;
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
-  c.pt = blockIdx.x * MLP_PTS_PER_WG + wave * MLP_PTS_PER_WAVE + (lane & 15);
+  c.pt = blockIdx.x * Core::PTS_PER_WG + wave * MLP_PTS_PER_WAVE + (lane & 15);
   c.valid = c.pt < P;
   c.ptc = c.valid ? c.pt : (P - 1);
   c.q = lane >> 4;
@@ -123,11 +124,6 @@ __device__ __forceinline__ void load_input_tiles(v4f (&in0)[5], const msdf_plan_
     for (int t = 0; t < 2; ++t)
       if (t < plan.aux_tiles) in0[3 + t] = aux_load_tile<LM>(aux, av, plan.aux_tiles, t, c.ptc, c.q);
   }
-}
-
-__device__ __forceinline__ void load_bias(v4f (&acc)[MT], const float* __restrict__ b, const int ot, const int q) {
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = (t < ot) ? *(const v4f*)(b + 16 * t + 4 * q) : V4ZERO;
 }
 
 // sdf row of the output layer as a dot product over the last hidden activation
@@ -305,7 +301,7 @@ __device__ __forceinline__ void sdf_forward_body(const msdf_plan_t& plan, const 
                                                  const float* __restrict__ aux, const AuxView av, const int P,
                                                  const float clamp_radius, const float sphere_scale,
                                                  float* __restrict__ sdf_out, void* lds) {
-  const PointCtx c = load_point(x, P);
+  const PointCtx c = load_point<Core>(x, P);
   v4f in[MT], acc[MT];
   const int in0_tiles = plan.e_tiles + plan.aux_tiles;
   {
@@ -348,7 +344,7 @@ typedef msdf_fg_args_t FgArgs;
 template <class Core>
 __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const FgArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  const PointCtx c = load_point(a.x, a.P);
+  const PointCtx c = load_point<Core>(a.x, a.P);
   const AuxView av = {a.aux_C, a.aux_LC, a.P};
   v4f in[MT], acc[MT];
   const int nl = plan.n_layers;
@@ -365,7 +361,7 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     }
   }
   // workgroup-uniform on purpose: the gemm below contains barriers and cooperative weight staging
-  const bool want_feat = (int)(blockIdx.x * MLP_PTS_PER_WG) < a.n_feat;
+  const bool want_feat = (int)(blockIdx.x * Core::PTS_PER_WG) < a.n_feat;
 
   // ---------------- forward chain ----------------
   for (int l = 0; l < nl - 1; ++l) {
@@ -539,7 +535,7 @@ __device__ __forceinline__ void load_rbar(v4f (&rbar)[5], const msdf_plan_t& pla
 template <class Core>
 __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const BwArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  const PointCtx c = load_point(a.x, a.P);
+  const PointCtx c = load_point<Core>(a.x, a.P);
   const int nl = plan.n_layers;
   const size_t Pp = (size_t)a.P_pad;
   const bool live = c.valid && !(a.clamped != nullptr && a.clamped[c.ptc]);
@@ -667,12 +663,3 @@ __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const
       if (t < plan.aux_tiles) aux_store_tile<Core::AUX_LEVEL_MAJOR>(a.g_aux, av, plan.aux_tiles, t, c.pt, c.q, g_in_aux[t]);
   }
 }
-
-// ---------------------------------------------------------------------------
-// C-ABI
-// ---------------------------------------------------------------------------
-static int mlp_prepare(const void* fn) {
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_BYTES) == hipSuccess
-             ? MSDF_OK : MSDF_ERR_LAUNCH;
-}
-
