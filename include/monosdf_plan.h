@@ -8,6 +8,7 @@
 #ifndef MONOSDF_PLAN_H
 #define MONOSDF_PLAN_H
 
+#include <stdbool.h>
 #include <stdint.h>
 
 #define MSDF_MAX_TILES 17  /* 17 * 16 = 272 slots: 256 hidden + one spare tile */
@@ -70,7 +71,15 @@ typedef struct {
  * two operand buffers (msdf_wgrad: base0 = the saved activations, base1 = the feature tensor) -- the table holds no
  * device address, so it is built once per network and point count and never copied again (a table of absolute
  * addresses had to be re-sent, synchronously, whenever the allocator handed the step other blocks); the *_off fields
- * below them are float offsets into the partial buffer. */
+ * below them are float offsets into the partial buffer.
+ *
+ * The fp32 kernel (msdf_wgrad_k) runs an item on the wave grid of its class, msdf_wgrad_class(wx, wy):
+ *   WIDE     2 x 4 waves of 128 rows x 64 columns
+ *   COLS128  8 x 1 waves of 32 rows x 128 columns   (COLS96: x 96, COLS64: x 64)
+ *   THIN     1 x 8 waves of 32 rows x 32 columns
+ *   COLSUM   no matrix product; runs on the COLS64 grid
+ * the bf16x3 kernel (msdf_wgrad_b16_k) on 8 x 1 waves of 32 x 64 where msdf_wgrad_b16_narrow(wx, wy), else on 2 x 4
+ * waves of 128 x 64.  The host's cost model (monosdf_amd/plan.py: ITEM_CLASSES) is keyed by the same classes. */
 typedef struct {
   int64_t x;                    /* float offset of X [P_pad, x_ld] in its buffer */
   int64_t y;                    /* float offset of Y [P_pad, y_ld] */
@@ -80,9 +89,54 @@ typedef struct {
   int64_t vrow_off;             /* [n_splits][wy] or < 0 */
   int32_t x_ld, y_ld;           /* row pitches of X and Y */
   int32_t wx, wy;               /* multiples of 16, <= 256; wy == 0: column sums only */
-  int32_t n_splits;             /* this item's share of the points is cut into n_splits workgroups */
+  int32_t n_splits;             /* the item's P_pad / MSDF_WGRAD_STAGE_POINTS stages are cut into n_splits workgroups:
+                                   split s takes the stages msdf_wgrad_split_range gives it */
   int32_t bufs;                 /* buffer index (0 / 1) of x | y << 8 | v << 16 (0xff: none) */
 } msdf_wgrad_item_t;
+
+/* ---- the weight-gradient schedule: stage size, item classes, split ranges (host and device) ---- */
+#if defined(__HIPCC__)
+#define MSDF_HD __host__ __device__
+#else
+#define MSDF_HD
+#endif
+
+#define MSDF_WGRAD_STAGE_POINTS 32   /* points per LDS stage; P_pad is a multiple */
+
+enum {                        /* widest first: the order of the host's cost table */
+  MSDF_WGRAD_WIDE = 0,        /* more than 128 columns */
+  MSDF_WGRAD_COLS128,         /* <= 128 columns */
+  MSDF_WGRAD_COLS96,          /* <= 96 */
+  MSDF_WGRAD_COLS64,          /* <= 64 */
+  MSDF_WGRAD_THIN,            /* <= 32 rows and more than 32 columns */
+  MSDF_WGRAD_COLSUM,          /* wy == 0: column sums only */
+  MSDF_WGRAD_N_CLASSES
+};
+
+static inline MSDF_HD int msdf_wgrad_class(const int wx, const int wy) {
+  if (wx <= 32 && wy > 32) return MSDF_WGRAD_THIN;
+  if (wy <= 64) return wy == 0 ? MSDF_WGRAD_COLSUM : MSDF_WGRAD_COLS64;
+  if (wy <= 96) return MSDF_WGRAD_COLS96;
+  if (wy <= 128) return MSDF_WGRAD_COLS128;
+  return MSDF_WGRAD_WIDE;
+}
+
+/* the bf16x3 kernel's two grids.  Not a function of the class above: 32 rows x 64 columns is THIN there, narrow here */
+static inline MSDF_HD bool msdf_wgrad_b16_narrow(const int wx, const int wy) {
+  (void)wx;
+  return wy <= 64;
+}
+
+/* stages [*begin, *end) of split `split`: a ceiling division, clipped to n_stages; trailing splits may be short or
+ * empty (*begin == *end, possibly behind n_stages) */
+static inline MSDF_HD void msdf_wgrad_split_range(const int n_stages, const int n_splits, const int split,
+                                                  int* begin, int* end) {
+  const int per = (n_stages + n_splits - 1) / n_splits;
+  const int b = split * per;
+  const int e = n_stages < b + per ? n_stages : b + per;
+  *begin = b;
+  *end = b + (e - b > 0 ? e - b : 0);
+}
 
 /* one reduction rule: dst[rowmap[i]*dst_ld + colmap[j]] = scale * sum_b PART[b][i*wy + j] */
 typedef struct {

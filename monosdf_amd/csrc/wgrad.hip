@@ -15,7 +15,7 @@
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 #define WG_THREADS 512
-#define WG_NP 32                               // points per LDS stage: one barrier per 128 MFMAs of each wave
+#define WG_NP MSDF_WGRAD_STAGE_POINTS          // points per LDS stage: one barrier per 128 MFMAs of each wave
 #define WG_NBUF 2                              // double buffered (a stage is ~8 us of matrix products)
 #define WG_TILE_F (WG_NP * 256)                // floats per operand tile
 #define WG_STAGE_F (2 * WG_TILE_F + 64)        // X tile, Y tile, v[NP] (+pad)
@@ -61,24 +61,43 @@ __device__ __forceinline__ void wg_wait_outstanding(const int stages_behind) {
   }
 }
 
+// What both kernels need of an item before their stage loops: its operands (the `bufs` bytes choose base0 / base1,
+// 0xff: no v) and the stages [s_begin, s_begin + n_st) of this split.
+struct wg_operands {
+  const float *X, *Y, *V;
+  bool do_mm;
+  int s_begin, n_st;
+};
+
+__device__ __forceinline__ wg_operands wg_resolve(const msdf_wgrad_item_t& it, const int split, const int P_pad,
+                                                  const float* __restrict__ base0, const float* __restrict__ base1) {
+  const float* const base[2] = {base0, base1};
+  wg_operands op;
+  int s_end;
+  msdf_wgrad_split_range(P_pad / WG_NP, it.n_splits, split, &op.s_begin, &s_end);
+  op.n_st = s_end - op.s_begin;
+  op.X = base[(it.bufs & 0xff) != 0] + it.x;
+  op.Y = base[((it.bufs >> 8) & 0xff) != 0] + it.y;
+  const int bv = (it.bufs >> 16) & 0xff;
+  op.V = bv == 0xff ? nullptr : base[bv != 0] + it.v;
+  op.do_mm = it.wy > 0;
+  return op;
+}
+
 // The wave grid is a template parameter, not a branch inside the k loop: with the branch there, the accumulators of
 // the two variants met in phi nodes and every k step copied 32 accumulator registers behind an `s_nop 15`
 // that waited out the previous MFMA (a third of the matrix pipe's time).
-// NBN == 0: wide items, 2 x 4 waves of 128 rows x 64 columns; NBN = 2, 3, 4: items of <= 32 NBN columns (the PE /
-// PE + hash-feature / skip blocks), 8 x 1 waves of 32 rows x 32 NBN columns so that all four SIMDs work -- an
-// 80-column item on the wide grid keeps the waves of two SIMDs idle and takes as long as a 256-column one.
-// NBN == -1: items of <= 32 rows, 1 x 8 waves of 32 rows x 32 columns.
+// NBN names the grid of an item class (msdf_wgrad_class, include/monosdf_plan.h): 0 wide; 2, 3, 4 the 8 x 1 grids of
+// 32 NBN columns (the PE / PE + hash-feature / skip blocks: all four SIMDs work, where an 80-column item on the wide
+// grid keeps the waves of two SIMDs idle and takes as long as a 256-column one); -1 thin.
 template <int NBN>
 __device__ __forceinline__ void wgrad_body(const msdf_wgrad_item_t& it, const int split,
                                            float* __restrict__ part, const int P_pad, float* lds_f,
                                            const float* __restrict__ base0, const float* __restrict__ base1) {
-  const int n_splits = it.n_splits;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // wide items: 2 x 4 waves, 128 rows x 64 cols each (4 x 2 MFMA tiles per wave);
-  // narrow items (wy <= 32 NBN): 8 x 1 waves, 32 rows x 32 NBN cols each, so all 8 waves (all 4 SIMDs) work
-  // thin items (wx <= 32 rows, e.g. the colour network's 3-row output layer): 1 x 8 waves, 32 rows x 32 cols each
+  // wide: 4 x 2 MFMA tiles per wave; narrow: 1 x NBN; thin (e.g. the colour network's 3-row output layer): 1 x 1
   constexpr bool narrow = NBN > 0;
   constexpr bool thin = NBN < 0;
   const int wi = thin ? 0 : narrow ? wave : (wave >> 2), wj = thin ? wave : narrow ? 0 : (wave & 3);
@@ -86,17 +105,10 @@ __device__ __forceinline__ void wgrad_body(const msdf_wgrad_item_t& it, const in
   constexpr int na = (narrow || thin) ? 1 : 4;
   constexpr int nb = thin ? 1 : narrow ? NBN : 2;
 
-  // point range of this split, in stages of WG_NP points
-  const int n_stages_total = P_pad / WG_NP;
-  const int per = (n_stages_total + n_splits - 1) / n_splits;
-  const int s_begin = split * per;
-  const int s_end = min(n_stages_total, s_begin + per);
-  const int n_st = max(0, s_end - s_begin);
-
-  const float* X = ((it.bufs & 0xff) ? base1 : base0) + it.x;
-  const float* Y = (((it.bufs >> 8) & 0xff) ? base1 : base0) + it.y;
-  const float* V = (((it.bufs >> 16) & 0xff) == 0xff) ? nullptr : ((((it.bufs >> 16) & 0xff) ? base1 : base0) + it.v);
-  const bool do_mm = it.wy > 0;
+  const wg_operands op = wg_resolve(it, split, P_pad, base0, base1);
+  const float *X = op.X, *Y = op.Y, *V = op.V;
+  const bool do_mm = op.do_mm;
+  const int s_begin = op.s_begin, n_st = op.n_st;
 
   v16f acc[na][nb];
 #pragma unroll
@@ -124,9 +136,8 @@ __device__ __forceinline__ void wgrad_body(const msdf_wgrad_item_t& it, const in
     else wg_issue_first_piece(X + p0 * it.x_ld, it.x_ld, it.wx, base, lane);   // column sums only: keeps the count uniform
     // per-point scalar (or, without one, a re-copy of 64 floats of X): one 4-byte-per-lane piece
     const float* vsrc = (V != nullptr) ? V + p0 + min(lane, WG_NP - 1) : X + p0 * it.x_ld + min(lane, 15);
-    float* vdst = (V != nullptr) ? base + 2 * WG_TILE_F : base + 2 * WG_TILE_F;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)vsrc,
-                                     (__attribute__((address_space(3))) void*)vdst, 4, 0, 0);
+                                     (__attribute__((address_space(3))) void*)(base + 2 * WG_TILE_F), 4, 0, 0);
   };
 
   // prologue: WG_NBUF - 1 stages in flight
@@ -208,7 +219,8 @@ msdf_wgrad_k(const msdf_wgrad_item_t* __restrict__ items, const int* __restrict_
   extern __shared__ float lds_f[];
   const msdf_wgrad_item_t it = items[wg_map[2 * blockIdx.x]];
   const int split = wg_map[2 * blockIdx.x + 1];
-  // wide items: 2 x 4 waves of 128 x 64; items of <= 128 columns: 8 x 1 waves of 32 x (64 | 96 | 128)
+  // msdf_wgrad_class (include/monosdf_plan.h) written out, column sums on the <= 64 grid: dispatching on the function's
+  // value gave every body other registers and another instruction order
   if (it.wx <= 32 && it.wy > 32) wgrad_body<-1>(it, split, part, P_pad, lds_f, base0, base1);
   else if (it.wy <= 64) wgrad_body<2>(it, split, part, P_pad, lds_f, base0, base1);
   else if (it.wy <= 96) wgrad_body<3>(it, split, part, P_pad, lds_f, base0, base1);
@@ -230,7 +242,6 @@ msdf_wgrad_k(const msdf_wgrad_item_t* __restrict__ items, const int* __restrict_
 typedef __bf16 wv8bf __attribute__((ext_vector_type(8)));
 typedef float wv4f __attribute__((ext_vector_type(4)));
 
-#define WB_NP 32
 #define WB_IMG_V8 (2 * 16 * 2 * 64)              // 16-byte elements per stage image
 #define WB_LDS_BYTES (2 * WB_IMG_V8 * 16)        // 128 KB
 
@@ -250,26 +261,19 @@ __device__ __forceinline__ void wgrad_b16_body(const msdf_wgrad_item_t& it, cons
                                                float* __restrict__ part,
                                                const int P_pad, wv8bf* lds_img,
                                                const float* __restrict__ base0, const float* __restrict__ base1) {
-  const int n_splits = it.n_splits;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // wide items: 2 x 4 waves of 128 rows x 64 cols (8 x 4 tiles); narrow (wy <= 64): 8 x 1 waves of 32 x 64
+  // wide: 8 x 4 tiles of 16 x 16 per wave; narrow (msdf_wgrad_b16_narrow): 2 x 4
   constexpr bool narrow = NARROW;
   const int wi = narrow ? wave : (wave >> 2), wj = narrow ? 0 : (wave & 3);
   const int i_base = narrow ? 32 * wi : 128 * wi, j_base = 64 * wj;
   constexpr int na = narrow ? 2 : 8;
 
-  const int n_stages_total = P_pad / WB_NP;
-  const int per = (n_stages_total + n_splits - 1) / n_splits;
-  const int s_begin = split * per;
-  const int s_end = min(n_stages_total, s_begin + per);
-  const int n_st = max(0, s_end - s_begin);
-
-  const float* X = ((it.bufs & 0xff) ? base1 : base0) + it.x;
-  const float* Y = (((it.bufs >> 8) & 0xff) ? base1 : base0) + it.y;
-  const float* V = (((it.bufs >> 16) & 0xff) == 0xff) ? nullptr : ((((it.bufs >> 16) & 0xff) ? base1 : base0) + it.v);
-  const bool do_mm = it.wy > 0;
+  const wg_operands op = wg_resolve(it, split, P_pad, base0, base1);
+  const float *X = op.X, *Y = op.Y, *V = op.V;
+  const bool do_mm = op.do_mm;
+  const int s_begin = op.s_begin, n_st = op.n_st;
   const bool want_vrow = it.vrow_off >= 0;
 
   wv4f acc[na][4];
@@ -289,7 +293,7 @@ __device__ __forceinline__ void wgrad_b16_body(const msdf_wgrad_item_t& it, cons
   float colsum = 0.f, vrow = 0.f;
 
   auto load = [&](const int j) {
-    const size_t p0 = (size_t)(s_begin + j) * WB_NP;
+    const size_t p0 = (size_t)(s_begin + j) * WG_NP;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const size_t pu = p0 + 8 * (kh + 2 * u);
@@ -302,7 +306,7 @@ __device__ __forceinline__ void wgrad_b16_body(const msdf_wgrad_item_t& it, cons
   };
   auto store = [&](const int j) {
     wv8bf* img = lds_img + (j & 1) * WB_IMG_V8;
-    const size_t p0 = (size_t)(s_begin + j) * WB_NP;
+    const size_t p0 = (size_t)(s_begin + j) * WG_NP;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int kq = kh + 2 * u;
@@ -402,7 +406,7 @@ msdf_wgrad_b16_k(const msdf_wgrad_item_t* __restrict__ items, const int* __restr
   extern __shared__ wv8bf lds_img[];
   const msdf_wgrad_item_t it = items[wg_map[2 * blockIdx.x]];
   const int split = wg_map[2 * blockIdx.x + 1];
-  if (it.wy <= 64) wgrad_b16_body<true>(it, split, part, P_pad, lds_img, base0, base1);
+  if (msdf_wgrad_b16_narrow(it.wx, it.wy)) wgrad_b16_body<true>(it, split, part, P_pad, lds_img, base0, base1);
   else wgrad_b16_body<false>(it, split, part, P_pad, lds_img, base0, base1);
 }
 
@@ -433,28 +437,25 @@ msdf_reduce_k(const msdf_reduce_rule_t* __restrict__ rules, const int* __restric
   }
 }
 
+typedef void (*wg_kernel_t)(const msdf_wgrad_item_t*, const int*, float*, int, const float*, const float*);
+
 extern "C" int msdf_wgrad(const msdf_wgrad_item_t* items_dev, const int32_t* wg_map_dev, int n_wgs,
                           float* partials, int P_pad, int precision, const float* base0, const float* base1,
                           void* stream) {
-  if (n_wgs < 0 || P_pad < 0 || (P_pad % WB_NP) != 0) return MSDF_ERR_ARG;
+  if (n_wgs < 0 || P_pad < 0 || (P_pad % MSDF_WGRAD_STAGE_POINTS) != 0) return MSDF_ERR_ARG;
   if (n_wgs > 0 && P_pad > 0 && base0 == nullptr) return MSDF_ERR_ARG;
   if (n_wgs == 0 || P_pad == 0) return MSDF_OK;
-  if (precision == MSDF_PRECISION_BF16X3) {
-    if (hipFuncSetAttribute((const void*)msdf_wgrad_b16_k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WB_LDS_BYTES) != hipSuccess)
-      return MSDF_ERR_LAUNCH;
-    msdf_wgrad_b16_k<<<n_wgs, WG_THREADS, WB_LDS_BYTES, (hipStream_t)stream>>>(items_dev, wg_map_dev, partials,
-                                                                               P_pad, base0, base1);
-    return msdf_check_launch();
-  }
   // BF16X6 networks take the fp32 kernel: both operands are saved fp32 activations, a three-plane image of a stage
   // would not fit the LDS double buffer, and the fp32 matrix instructions are exact where bf16x6 is fp32-grade
-  if (precision != MSDF_PRECISION_F32 && precision != MSDF_PRECISION_BF16X6) return MSDF_ERR_ARG;
-  if (hipFuncSetAttribute((const void*)msdf_wgrad_k, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS_BYTES) !=
-      hipSuccess)
+  wg_kernel_t kernel;
+  int lds_bytes;
+  if (precision == MSDF_PRECISION_BF16X3) kernel = msdf_wgrad_b16_k, lds_bytes = WB_LDS_BYTES;
+  else if (precision == MSDF_PRECISION_F32 || precision == MSDF_PRECISION_BF16X6)
+    kernel = msdf_wgrad_k, lds_bytes = WG_LDS_BYTES;
+  else return MSDF_ERR_ARG;
+  if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
     return MSDF_ERR_LAUNCH;
-  msdf_wgrad_k<<<n_wgs, WG_THREADS, WG_LDS_BYTES, (hipStream_t)stream>>>(items_dev, wg_map_dev, partials,
-                                                                          P_pad, base0, base1);
+  kernel<<<n_wgs, WG_THREADS, lds_bytes, (hipStream_t)stream>>>(items_dev, wg_map_dev, partials, P_pad, base0, base1);
   return msdf_check_launch();
 }
 

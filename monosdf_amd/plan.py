@@ -7,6 +7,7 @@ column of a reference weight matrix (reference: code/model/network.py:43-75 for
 the SDF network's dims/skip logic, 344-384 for the colour network) each slot
 carries; padding slots map to -1 and get zero weights.
 """
+import collections
 import ctypes as C
 import math
 
@@ -282,14 +283,60 @@ def color_workspace(mp, P_pad):
 # ---------------------------------------------------------------------------
 # weight-gradient work items + reduction rules
 # ---------------------------------------------------------------------------
+# The schedule rules below restate include/monosdf_plan.h (MSDF_WGRAD_STAGE_POINTS, msdf_wgrad_class,
+# msdf_wgrad_split_range), which is what the kernels run; tests/test_host_logic.py compares the two exhaustively.
+STAGE_POINTS = 32
+
+# Item classes = the wave grids of msdf_wgrad_k, widest first; a class is its index here (the value of the header's enum).
+# stage_us, fixed_us: microseconds per stage of a workgroup and fixed cost of a workgroup, MI355X: one item alone over
+# 1 / 2 / 4 rounds of workgroups (scripts/bench_wgrad.py calib), then fitted to 80 timed split plans of the three
+# networks (`target` sweeps; profiles/r04_wgrad_splits.md: rms error 3 % for workgroups of <= 500 us).
+# corun: factor on stage_us measured while the class runs beside wide workgroups (choose_splits), None: not measured
+ItemClass = collections.namedtuple('ItemClass', 'name stage_us fixed_us corun')
+ITEM_CLASSES = (ItemClass('wide', 8.4, 6.0, None),
+                ItemClass('cols128', 5.2, 6.0, 1.45),
+                ItemClass('cols96', 4.1, 5.0, 1.45),
+                ItemClass('cols64', 3.0, 8.0, None),
+                ItemClass('thin', 2.2, 6.0, None),
+                ItemClass('colsum', 1.45, 2.0, None))
+WIDE, COLS128, COLS96, COLS64, THIN, COLSUM = range(len(ITEM_CLASSES))
+
+
+def item_class(wx, wy):
+    """msdf_wgrad_class: the class of a wx x wy item."""
+    if wy == 0:
+        return COLSUM
+    if wx <= 32 and wy > 32:
+        return THIN
+    if wy <= 64:
+        return COLS64
+    if wy <= 96:
+        return COLS96
+    if wy <= 128:
+        return COLS128
+    return WIDE
+
+
+def split_range(n_stages, n_splits, split):
+    """msdf_wgrad_split_range: stages [begin, end) of one split -- a ceiling division, clipped (a split may be empty)."""
+    per = -(-n_stages // n_splits)
+    begin = split * per
+    return begin, max(begin, min(n_stages, begin + per))
+
+
 class WgradProgram:
     """Work items (absolute device addresses are filled in per call), reduce rules and the
-    workgroup -> (item, split) map.  Every item cuts its point range into its own number of splits,
-    chosen so that all workgroups of a launch run about equally long and fill the 256 CUs."""
+    workgroup -> (item, split) map of one launch over P_pad points.  Every item cuts its point range into its own
+    number of splits, chosen so that all workgroups of a launch run about equally long and fill the 256 CUs.
+    The builders below always give P_pad.  A hand-built program may leave it out: it computes the same, but it has no
+    durations (stages_per_wg raises) and its workgroups run in item order."""
 
-    def __init__(self, split_fn):
-        self.split_fn = split_fn
-        self.items = []      # dicts: x, y, v = (buffer name, float offset); part/colsum/vrow offsets; n_splits
+    def __init__(self, split_fn, P_pad=None):
+        assert P_pad is None or (P_pad > 0 and P_pad % STAGE_POINTS == 0), P_pad
+        self.split_fn = split_fn      # item class -> n_splits
+        self.P_pad = P_pad
+        self.n_stages = None if P_pad is None else P_pad // STAGE_POINTS
+        self.items = []      # dicts: x, y, v = (buffer name, float offset); part/colsum/vrow offsets; n_splits; cls
         self.rules = []      # ReduceRule
         self.part_f = 0
 
@@ -298,36 +345,17 @@ class WgradProgram:
         self.part_f += n
         return off
 
-    @staticmethod
-    def weight(wx, wy):
-        """Class of an item = the wave grid msdf_wgrad_k runs it on (csrc/wgrad.hip), named by the relative duration of one
-        32-point stage: 1.0 wide (2 x 4 waves of 128 x 64), 0.6 / 0.5 / 0.3 the 8 x 1 grids of <= 128 / 96 / 64 columns,
-        0.2 thin (<= 32 rows: 1 x 8 waves of 32 x 32), 0.0 column sums only."""
-        if wy == 0:
-            return 0.0
-        if wx <= 32 and wy > 32:
-            return 0.2
-        if wy <= 128:
-            return {2: 0.3, 3: 0.5, 4: 0.6}[max(2, (wy + 31) // 32)]
-        return 1.0
-
-    # class -> (microseconds per 32-point stage of a workgroup, fixed cost of a workgroup), MI355X: one item alone over
-    # 1 / 2 / 4 rounds of workgroups (scripts/bench_wgrad.py calib), then fitted to 80 timed split plans of the three
-    # networks (`target` sweeps; profiles/r04_wgrad_splits.md: rms error 3 % for workgroups of <= 500 us)
-    CLASS_COST_US = {1.0: (8.4, 6.0), 0.6: (5.2, 6.0), 0.5: (4.1, 5.0), 0.3: (3.0, 8.0), 0.2: (2.2, 6.0),
-                     0.0: (1.45, 2.0)}
-    CORUN_SLOWDOWN = {0.5: 1.45, 0.6: 1.45}
     N_CU = 256
     REDUCE_US_PER_MB = 0.54          # msdf_reduce_k reads the partial blocks at ~1.85 TB/s
 
     def splits(self, wx, wy):
-        return self.split_fn(self.weight(wx, wy))
+        return self.split_fn(item_class(wx, wy))
 
     def add_item(self, x, x_ld, wx, y, y_ld, wy, part_off, n_splits, colsum_off=-1, v=None, vrow_off=-1):
         assert wx % 16 == 0 and wy % 16 == 0 and wx <= 256 and wy <= 256, (wx, wy)
         self.items.append(dict(x=x, y=y, v=v, x_ld=x_ld, y_ld=y_ld, wx=wx, wy=wy, part_off=part_off,
                                colsum_off=colsum_off, vrow_off=vrow_off, n_splits=n_splits,
-                               weight=self.weight(wx, wy)))
+                               cls=item_class(wx, wy)))
 
     def add_rule(self, part_off, n_blocks, wx, wy, rowmap_off, colmap_off, dst_off, dst_ld, scale,
                  fixed_row=0):
@@ -356,14 +384,23 @@ class WgradProgram:
     def rules_bytes(self):
         return np.frombuffer(b''.join(bytes(r) for r in self.rules), dtype=np.uint8).copy()
 
+    def stages_per_wg(self, it):
+        """Stages of the longest workgroup of item `it`: its first split."""
+        if self.n_stages is None:
+            raise RuntimeError('monosdf_amd: a WgradProgram built without P_pad has no stage counts')
+        begin, end = split_range(self.n_stages, it['n_splits'], 0)
+        return end - begin
+
     def wg_duration_us(self, it):
         """Modelled duration of one workgroup of item `it` (all its splits are equally long up to one stage)."""
-        tau, t0 = self.CLASS_COST_US[it['weight']]
-        return t0 + tau * it.get('stages_per_wg', 1)
+        c = ITEM_CLASSES[it['cls']]
+        return c.fixed_us + c.stage_us * self.stages_per_wg(it)
 
     def wg_map(self):
         """int32 (item, split) pairs; long workgroups first so the tail of the launch is made of short ones."""
-        order = sorted(range(len(self.items)), key=lambda i: -self.wg_duration_us(self.items[i]))
+        order = range(len(self.items))
+        if self.n_stages is not None:
+            order = sorted(order, key=lambda i: -self.wg_duration_us(self.items[i]))
         pairs = [(i, s) for i in order for s in range(self.items[i]['n_splits'])]
         return np.asarray(pairs, dtype=np.int32).reshape(-1)
 
@@ -397,7 +434,8 @@ def _makespan_us(durations, n_cu):
 
 
 _SPLIT_CACHE = {}
-# the second evaluation of a candidate plan slows EVERY class but the widest by 30 % (0 switches that off: comparison
+# the second evaluation of a candidate plan slows EVERY class but the widest (and those with a measured co-run factor) by
+# 30 % (0 switches that off: comparison
 # runs).  Stand-alone the colour network's launch is faster without it (0.27 against 0.33 ms: 96 instead of 77 splits of
 # its wide items, 314 workgroups), but inside the training step -- where that launch runs beside the scatter and the
 # SDF launch -- the plan that fits ONE round of the 256 CUs measured better: configs[2] 3.37 against 3.39 ms per step
@@ -426,15 +464,14 @@ def choose_splits(classes, n_stages, part_floats, target_us=None):
     key = (tuple(sorted(classes.items())), n_stages, tuple(sorted(part_floats.items())), target_us)
     if key in _SPLIT_CACHE:
         return _SPLIT_CACHE[key]
-    cost = WgradProgram.CLASS_COST_US
-    top = max(classes)
+    top = min(classes)               # ITEM_CLASSES is ordered widest first
     best = None
     # workgroups longer than ~500 us are outside what the model was fitted on (and measured 10-20 % slower than it says:
     # the narrow classes are latency-bound when they run for that long beside wide workgroups).  Inside that range the
     # model ranks plans as the GPU does -- a same-process sweep of the wide split count (scripts/bench_wgrad.py fine,
     # profiles/r04_wgrad_splits.md): the cliffs where the wide workgroups spill into one more round of the 256 CUs and
     # the best plan of each of the three networks are where it puts them
-    tau_top, t0_top = cost[top]
+    tau_top, t0_top = ITEM_CLASSES[top].stage_us, ITEM_CLASSES[top].fixed_us
     if target_us is None:
         # every split count of the widest class whose workgroups last 100 ... 500 us, each with its own duration as D
         s_lo = max(1, math.ceil(n_stages * tau_top / (500.0 - t0_top)))
@@ -445,7 +482,7 @@ def choose_splits(classes, n_stages, part_floats, target_us=None):
     for D in cands:
         S, part = {}, 0.0
         for c, n_items in classes.items():
-            tau, t0 = cost[c]
+            tau, t0 = ITEM_CLASSES[c].stage_us, ITEM_CLASSES[c].fixed_us
             d = D if c == top else 0.5 * D
             S[c] = int(min(n_stages, max(1, math.ceil(n_stages * tau / max(d - t0, tau)))))
             part += part_floats.get(c, 0) * S[c]
@@ -458,9 +495,9 @@ def choose_splits(classes, n_stages, part_floats, target_us=None):
             # to be good either way
             durs = []
             for c, n_items in classes.items():
-                tau, t0 = cost[c]
-                if corun and c in WgradProgram.CORUN_SLOWDOWN:
-                    tau *= WgradProgram.CORUN_SLOWDOWN[c]
+                tau, t0 = ITEM_CLASSES[c].stage_us, ITEM_CLASSES[c].fixed_us
+                if corun and ITEM_CLASSES[c].corun is not None:
+                    tau *= ITEM_CLASSES[c].corun
                 elif corun and c != top and _ALL_NARROW_SLOW:
                     tau *= 1.3
                 durs += [t0 + tau * -(-n_stages // S[c])] * (n_items * S[c])
@@ -473,21 +510,27 @@ def choose_splits(classes, n_stages, part_floats, target_us=None):
     return best[1]
 
 
-def balanced_program(build, mp, P_pad, splits=None, target_us=None):
-    """The weight-gradient program of a network with its split counts chosen by choose_splits (or given per class;
-    target_us: the workgroup duration instead of the modelled optimum -- tuning runs)."""
-    if splits is None:
-        probe = build(mp, P_pad, lambda w: 1)
-        classes, part = {}, {}
-        for it in probe.items:
-            classes[it['weight']] = classes.get(it['weight'], 0) + 1
-            part[it['weight']] = part.get(it['weight'], 0) + it['wx'] * max(it['wy'], 1)
-        splits = choose_splits(classes, max(1, P_pad // 32), part, target_us)
-    prog = build(mp, P_pad, lambda w: splits[w])
-    n_stages = max(1, P_pad // 32)
-    for it in prog.items:
-        it['stages_per_wg'] = -(-n_stages // it['n_splits'])
-    return prog
+def balanced_program(build, mp, P_pad, target_us=None):
+    """The weight-gradient program of a network with its split counts chosen by choose_splits (target_us: the
+    workgroup duration instead of the modelled optimum -- tuning runs)."""
+    probe = build(mp, P_pad, lambda c: 1)
+    classes, part = {}, {}
+    for it in probe.items:
+        classes[it['cls']] = classes.get(it['cls'], 0) + 1
+        part[it['cls']] = part.get(it['cls'], 0) + it['wx'] * max(it['wy'], 1)
+    splits = choose_splits(classes, probe.n_stages, part, target_us)
+    return build(mp, P_pad, lambda c: splits[c])
+
+
+UNIFORM_STAGES_PER_SPLIT = 54
+
+
+def uniform_program(build, mp, P_pad):
+    """The program of the bf16x3 kernel: the split model is fitted to the fp32 kernel (also what the bf16x6 core runs);
+    msdf_wgrad_b16_k has its own stage times and wave grids and keeps round 1's plan, the same split of about
+    UNIFORM_STAGES_PER_SPLIT stages for every item."""
+    S = max(1, -(-P_pad // (UNIFORM_STAGES_PER_SPLIT * STAGE_POINTS)))
+    return build(mp, P_pad, lambda c: S)
 
 
 def _col_parts(L, in0_tiles):
@@ -503,7 +546,7 @@ def build_sdf_wgrad(mp, P_pad, split_fn):
     P = mp.plan
     n = P.n_layers
     woff, _ = sdf_workspace(mp, P_pad)
-    prog = WgradProgram(split_fn)
+    prog = WgradProgram(split_fn, P_pad)
     dW_off, dB_off = mp.w_offsets, mp.b_offsets + mp.n_w     # gradient buffer: all dW then all db
     for l in range(n):
         L = P.layer[l]
@@ -562,7 +605,7 @@ def build_color_wgrad(mp, P_pad, split_fn):
     P = mp.plan
     nu = P.n_layers
     woff, _ = color_workspace(mp, P_pad)
-    prog = WgradProgram(split_fn)
+    prog = WgradProgram(split_fn, P_pad)
     dW_off, dB_off = mp.w_offsets, mp.b_offsets + mp.n_w
     # first layer: units 0 (feature columns) and 1 (misc columns) share a-bar_0
     for u in range(nu):

@@ -50,8 +50,6 @@ def run(prog, label, iters=10):
         once()
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
-    for it in prog.items:
-        it.setdefault('stages_per_wg', -(-(P_pad // 32) // it['n_splits']))
     model = planlib.model_launch_us(prog)
     print('%-60s WGs %4d  part %6.1f MB  %.3f ms  %.1f TFLOP/s (padded tiles)  model %.3f + reduce %.3f' % (
         label, wg_map.numel() // 2, 4e-6 * prog.part_f, ms, 2 * macs / ms / 1e9, 1e-3 * model[0], 1e-3 * model[1]), flush=True)
@@ -59,21 +57,21 @@ def run(prog, label, iters=10):
 
 
 prog = planlib.balanced_program(build, mp, P_pad)
-cls = sorted(set((it['weight'], it['n_splits']) for it in prog.items))
-print(which, 'items (wx, wy, weight, splits):', [(it['wx'], it['wy'], it['weight'], it['n_splits']) for it in prog.items])
-run(prog, 'library plan %s' % cls)
+cname = lambda it: planlib.ITEM_CLASSES[it['cls']].name
+class_splits = lambda pr: sorted(set((cname(it), it['n_splits']) for it in pr.items))
+print(which, 'items (wx, wy, class, splits):', [(it['wx'], it['wy'], cname(it), it['n_splits']) for it in prog.items])
+run(prog, 'library plan %s' % class_splits(prog))
 if sweep:
-    weights = sorted(set(it['weight'] for it in prog.items), reverse=True)
     if which == 'mlp':
         for S in (48, 56, 59, 61, 64, 68, 72, 85):
             run(build(mp, P_pad, lambda w, S=S: S), 'all items S=%d' % S)
     for Sw in (40, 51, 60, 64, 68, 76, 85, 102, 128, 153, 170):
         for f in (1.0, 0.6, 0.4):
             for Sc in (4, 16):
-                def fn(w, Sw=Sw, f=f, Sc=Sc):
-                    if w >= 1.0:
+                def fn(c, Sw=Sw, f=f, Sc=Sc):
+                    if c == planlib.WIDE:
                         return Sw
-                    if w == 0.0:
+                    if c == planlib.COLSUM:
                         return Sc
                     return max(1, int(round(Sw * f)))
                 run(build(mp, P_pad, fn), 'wide %d, narrow x%.1f, colsum %d' % (Sw, f, Sc), iters=5)
@@ -81,10 +79,10 @@ if sweep:
 
 def calibrate():
     """Per item class: time of a launch of that item alone with 256 / 512 / 1024 splits (1 / 2 / 4 rounds of the 256 CUs)
-    -> per-stage time and fixed cost of a workgroup (the constants of plan.WgradProgram.stage_us / WG_FIXED_US)."""
+    -> per-stage time and fixed cost of a workgroup (stage_us / fixed_us of plan.ITEM_CLASSES)."""
     import numpy as np
     seen = set()
-    n_stages = P_pad // 32
+    n_stages = P_pad // planlib.STAGE_POINTS
     for S in (256, 512, 1024):
         prog = build(mp, P_pad, lambda w, S=S: S)
         items = torch.from_numpy(prog.items_bytes()).to(dev)
@@ -113,7 +111,7 @@ def calibrate():
 if 'target' in sys.argv[2:]:
     for D in (80, 100, 115, 130, 150, 165, 180, 200, 215, 230, 245, 260, 280, 300, 325, 350, 375, 400, 435, 470, 510, 550, 600, 650, 720, 800):
         pr = planlib.balanced_program(build, mp, P_pad, target_us=D)
-        run(pr, 'target %4d us %s' % (D, sorted(set((it['weight'], it['n_splits']) for it in pr.items))), iters=8)
+        run(pr, 'target %4d us %s' % (D, class_splits(pr)), iters=8)
 if 'calib' in sys.argv[2:]:
     calibrate()
 
@@ -122,17 +120,17 @@ def fine():
     """Same process, interleaved repetitions: the chooser's plan against plans with the wide class pinned to a range of
     split counts (the other classes by the chooser's rule for that workgroup duration)."""
     import numpy as np
-    cost = planlib.WgradProgram.CLASS_COST_US
-    n_stages = P_pad // 32
+    wide = planlib.ITEM_CLASSES[planlib.WIDE]
+    n_stages = P_pad // planlib.STAGE_POINTS
     rng = {'mlp': range(54, 76), 'grid': list(range(76, 92)) + list(range(106, 118)), 'color': range(70, 100)}[which]
     progs = [('library', planlib.balanced_program(build, mp, P_pad))]
     for sw in rng:
-        D = cost[1.0][1] + cost[1.0][0] * -(-n_stages // sw)
+        D = wide.fixed_us + wide.stage_us * -(-n_stages // sw)
         progs.append(('wide %d' % sw, planlib.balanced_program(build, mp, P_pad, target_us=D)))
     res = {n: [] for n, _ in progs}
     for rep in range(3):
         for n, pr in progs:
-            res[n].append(run(pr, '%s %s' % (n, sorted(set((it['weight'], it['n_splits']) for it in pr.items))), iters=6))
+            res[n].append(run(pr, '%s %s' % (n, class_splits(pr)), iters=6))
     print('--- median of 3 ---')
     for n, _ in progs:
         print('%-12s %.3f ms' % (n, float(np.median(res[n]))))

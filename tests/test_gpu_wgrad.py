@@ -102,7 +102,7 @@ class Synth:
             self.regions.append((buf, off + c0, ld, w, kind))
             return (buf, off + c0)
 
-        prog = planlib.WgradProgram(lambda w: splits[0])
+        prog = planlib.WgradProgram(lambda w: splits[0], P_pad)
         n = wx * wy
         x_ld = wx + x_pad
         y_ld = x_ld if y_is_x else y_c0 + wy + y_pad
@@ -326,7 +326,7 @@ REAL = [('mlp', 32), ('mlp', 64), ('mlp', 4096), ('mlp', 104448), ('grid', 32), 
 
 @pytest.mark.parametrize('name,P_pad', REAL, ids=['%s_%d' % r for r in REAL])
 def test_real_programs(name, P_pad):
-    """The library's own programs (fp32: balanced_program; bf16x3: the uniform split of FusedMlp.wgrad_program) over
+    """The library's own programs (fp32: balanced_program; bf16x3: uniform_program) over
     a synthetic integer workspace, flat gradient [n_w + n_b] compared element by element."""
     from monosdf_amd import ops
     mp, build, wsfn, P_head = wn.headline_plans()[name]
@@ -344,7 +344,7 @@ def test_real_programs(name, P_pad):
     for precision, pname in ((F32, 'fp32'), (BF16X3, 'bf16x3')):
         prog = ops.FusedMlp(mp, torch.device('cuda'), precision=pname).wgrad_program(P_pad)['prog']
         if pname == 'bf16x3':
-            assert {it['n_splits'] for it in prog.items} == {max(1, (P_pad + 1727) // 1728)}
+            assert {it['n_splits'] for it in prog.items} == {max(1, -(-P_pad // (planlib.UNIFORM_STAGES_PER_SPLIT * planlib.STAGE_POINTS)))}
         assert_exact_precondition(prog, bufs, P_pad)
         # integer data: lo = 0, both kernels compute the plain product (the item sums are shared through `cache`)
         want = wn.reference_grad(prog, mp.maps_np, bufs, P_pad, n_total, init=np.nan, mode='fp32', cache=cache)
@@ -379,11 +379,11 @@ def test_normal_data_within_the_summation_bound_and_reproducible():
     256 CUs); all copies and a second run of the whole program must be bit-equal (fixed order, no float atomics)."""
     K = 104448
     mlp, col = wn.headline_plans()['mlp'], wn.headline_plans()['color']
-    S = {it['weight']: it['n_splits'] for it in planlib.balanced_program(mlp[1], mlp[0], K).items}
-    S.update({it['weight']: it['n_splits'] for it in planlib.balanced_program(col[1], col[0], K).items
-              if it['weight'] == 0.2})
-    shapes = [(256, 256, S[1.0], 12), (256, 48, S[0.3], 1), (16, 256, S[0.2], 1)]
-    prog = planlib.WgradProgram(lambda w: 1)
+    S = {it['cls']: it['n_splits'] for it in planlib.balanced_program(mlp[1], mlp[0], K).items}
+    S.update({it['cls']: it['n_splits'] for it in planlib.balanced_program(col[1], col[0], K).items
+              if it['cls'] == planlib.THIN})
+    shapes = [(256, 256, S[planlib.WIDE], 12), (256, 48, S[planlib.COLS64], 1), (16, 256, S[planlib.THIN], 1)]
+    prog = planlib.WgradProgram(lambda w: 1, K)
     n_total, outs = 0, []
     xo = 0
     yo = K * 256

@@ -57,6 +57,56 @@ def test_struct_sizes_match_header():
         assert ctypes.sizeof(cls) == sizes[n], (n, ctypes.sizeof(cls), sizes[n])
 
 
+def test_wgrad_schedule_rules_match_header():
+    """plan.item_class / split_range / STAGE_POINTS and the class table against the C statement of the same rules in
+    monosdf_plan.h (what the kernels dispatch on), for every item shape and the split counts listed below."""
+    import subprocess, tempfile
+    from monosdf_amd import plan as planlib
+    names = ['WIDE', 'COLS128', 'COLS96', 'COLS64', 'THIN', 'COLSUM']
+    src = r'''#include <stdio.h>
+#include "monosdf_plan.h"
+int main(void) {
+  const int stages[5] = {1, 2, 7, 32, 3264};
+  printf("stage %d\nclasses %d %d %d %d %d %d %d\n", MSDF_WGRAD_STAGE_POINTS, MSDF_WGRAD_WIDE, MSDF_WGRAD_COLS128,
+         MSDF_WGRAD_COLS96, MSDF_WGRAD_COLS64, MSDF_WGRAD_THIN, MSDF_WGRAD_COLSUM, MSDF_WGRAD_N_CLASSES);
+  for (int wx = 16; wx <= 256; wx += 16)
+    for (int wy = 0; wy <= 256; wy += 16)
+      printf("shape %d %d %d %d\n", wx, wy, msdf_wgrad_class(wx, wy), msdf_wgrad_b16_narrow(wx, wy));
+  for (int i = 0; i < 5; ++i) {
+    const int n = stages[i], splits[6] = {1, 2, 3, 7, 54, n};
+    for (int j = 0; j < 6; ++j)
+      for (int s = 0; s < splits[j]; ++s) {
+        int b, e;
+        msdf_wgrad_split_range(n, splits[j], s, &b, &e);
+        printf("range %d %d %d %d %d\n", n, splits[j], s, b, e);
+      }
+  }
+  return 0;
+}'''
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, 't.c'), 'w').write(src)
+        subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'),
+                               os.path.join(d, 't.c'), '-o', os.path.join(d, 't')])
+        lines = [l.split() for l in subprocess.check_output([os.path.join(d, 't')]).decode().splitlines()]
+    rows = lambda tag: [tuple(map(int, l[1:])) for l in lines if l[0] == tag]
+    assert rows('stage') == [(planlib.STAGE_POINTS,)]
+    assert rows('classes') == [tuple(getattr(planlib, n) for n in names) + (len(planlib.ITEM_CLASSES),)]
+    assert [c.name.upper() for c in planlib.ITEM_CLASSES] == names
+    shapes = rows('shape')
+    assert [s[:2] for s in shapes] == [(wx, wy) for wx in range(16, 257, 16) for wy in range(0, 257, 16)]
+    for wx, wy, cls, narrow in shapes:
+        assert planlib.item_class(wx, wy) == cls, (wx, wy)
+        assert narrow == (wy <= 64), (wx, wy)
+    # every class with costs is some shape's class and the other way round; the bf16x3 choice is no function of the class
+    assert {s[2] for s in shapes} == set(range(len(planlib.ITEM_CLASSES)))
+    assert {n for _, _, c, n in shapes if c == planlib.THIN} == {0, 1}
+    ranges = rows('range')
+    want = [(n, k, s) for n in (1, 2, 7, 32, 3264) for k in (1, 2, 3, 7, 54, n) for s in range(k)]
+    assert [r[:3] for r in ranges] == want
+    for n, k, s, b, e in ranges:
+        assert planlib.split_range(n, k, s) == (b, e), (n, k, s)
+
+
 def _slot_forward(mp, weights, biases, x, aux=None):
     """Numpy emulation of the kernels' slot-space forward (maps + scale only, no tiling)."""
     P = mp.plan
@@ -321,14 +371,15 @@ def test_weight_gradient_split_plan_covers_every_point_once(P_pad):
              (planlib.build_sdf_plan([(256, 71), (256, 256), (257, 256)], [4], 6, 32, True, 256), planlib.build_sdf_wgrad),
              (planlib.build_sdf_plan([(64, 39), (64, 64), (65, 64)], [], 6, 0, False, 64), planlib.build_sdf_wgrad),
              (planlib.build_color_plan([(256, 289), (256, 256), (3, 256)], 'idr', 4, 256), planlib.build_color_wgrad)]
-    n_stages = P_pad // 32
+    n_stages = P_pad // planlib.STAGE_POINTS
     for mp, build in plans:
         prog = planlib.balanced_program(build, mp, P_pad)
         assert prog.items
         for it in prog.items:
             assert 1 <= it['n_splits'] <= max(1, n_stages)
-            per = -(-n_stages // it['n_splits'])
-            assert per == it['stages_per_wg'] and per * it['n_splits'] >= n_stages
+            begin, end = planlib.split_range(n_stages, it['n_splits'], 0)
+            per = end - begin
+            assert per == prog.stages_per_wg(it) and per * it['n_splits'] >= n_stages
         pairs = prog.wg_map().reshape(-1, 2)
         want = {(i, s) for i, it in enumerate(prog.items) for s in range(it['n_splits'])}
         assert len(pairs) == len(want) and {tuple(p) for p in pairs.tolist()} == want

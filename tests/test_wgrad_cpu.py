@@ -1,6 +1,11 @@
 """Host-only checks of the weight-gradient restatement (tests/wgrad_numpy.py) and of the split arithmetic: the
 interpreter against a direct einsum on hand-built programs, and on the real programs of the four networks (results
 independent of the split counts, every gradient element written exactly once)."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -32,7 +37,7 @@ def test_interpreter_matches_einsum_on_a_hand_built_item():
     """One item with x_ld > wx, a column offset into Y, holed maps, scale != 1; a v-weighted row through fixed_row and
     column sums through a second rule; everything else keeps the initial value."""
     P_pad, wx, wy, x_ld, y_ld, c0, S = 96, 32, 48, 80, 112, 32, 2
-    prog = planlib.WgradProgram(lambda w: S)
+    prog = planlib.WgradProgram(lambda w: S, P_pad)
     part, cs, vr = prog.alloc(S * wx * wy), prog.alloc(S * wx), prog.alloc(S * wy)
     x_off, y_off, v_off = 16, 64, 7
     prog.add_item(('ws', x_off), x_ld, wx, ('feat', y_off + c0), y_ld, wy, part, S, colsum_off=cs,
@@ -74,7 +79,7 @@ def test_interpreter_matches_einsum_on_a_hand_built_item():
 
 def test_interpreter_adds_the_items_that_share_a_rule():
     P_pad, w = 64, 16
-    prog = planlib.WgradProgram(lambda w: 1)
+    prog = planlib.WgradProgram(lambda w: 1, P_pad)
     part = prog.alloc(3 * w * w + 4 * w * w)
     prog.add_item(('ws', 0), w, w, ('ws', P_pad * w), w, w, part, 3)
     prog.add_item(('ws', 2 * P_pad * w), w, w, ('ws', 3 * P_pad * w), w, w, part + 3 * w * w, 4)
@@ -92,7 +97,7 @@ def test_bf16x3_mode_is_the_three_product_definition():
     P_pad, w = 64, 16
     rng = np.random.default_rng(4)
     x = (rng.integers(1, 4, (2, P_pad, w)) + rng.integers(-3, 4, (2, P_pad, w)) * 2.0 ** -10).astype(np.float32)
-    prog = planlib.WgradProgram(lambda w: 1)
+    prog = planlib.WgradProgram(lambda w: 1, P_pad)
     prog.add_item(('ws', 0), w, w, ('ws', P_pad * w), w, w, prog.alloc(w * w), 1)
     prog.add_rule(0, 1, w, w, 0, 0, 0, w, 1.0)
     got = wn.reference_grad(prog, np.arange(w, dtype=np.int32), {'ws': x.reshape(-1)}, P_pad, w * w, mode='bf16x3')
@@ -129,9 +134,9 @@ def test_split_ranges_of_the_headline_programs_cover_every_stage_once(name):
     24 stages, split 82 none) and the 48-column items of the 8 x 256 network 50 splits (last one 30 of 66 stages); an
     empty split is exercised on the device by the synthetic cases of test_gpu_wgrad.py whatever the chooser does."""
     mp, build, _, P_pad = wn.headline_plans()[name]
-    n = P_pad // 32
+    n = P_pad // planlib.STAGE_POINTS
     pairs = {(n, it['n_splits']) for it in planlib.balanced_program(build, mp, P_pad).items}
-    pairs |= {(n, max(1, (P_pad + 1727) // 1728)), (9, 6), (3, 5), (67, 8), (1, 1)}
+    pairs |= {(n, max(1, -(-n // planlib.UNIFORM_STAGES_PER_SPLIT))), (9, 6), (3, 5), (67, 8), (1, 1)}
     for n_stages, n_splits in sorted(pairs):
         assert 1 <= n_splits
         ranges = wn.split_ranges(n_stages, n_splits)
@@ -141,3 +146,45 @@ def test_split_ranges_of_the_headline_programs_cover_every_stage_once(name):
             assert 0 <= b <= e <= n_stages or (b > n_stages and b == e)
             seen[b:e] += 1
         assert (seen == 1).all(), (n_stages, n_splits)
+
+
+# ---------------------------------------------------------------------------
+# the programs the library hands to the device, against digests recorded before the schedule rules were named
+# ---------------------------------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'wgrad_programs.json')
+DIGEST_P_PADS = (64, 640, 12800, 100352, 104448)
+
+
+def program_digests(names):
+    """'network/P_pad/kind' -> wn.program_digest of the balanced and the bf16x3 uniform program."""
+    out = {}
+    for name in names:
+        mp, build, _, _ = wn.headline_plans()[name]
+        for P_pad in DIGEST_P_PADS:
+            out['%s/%d/balanced' % (name, P_pad)] = wn.program_digest(planlib.balanced_program(build, mp, P_pad), mp)
+            out['%s/%d/bf16x3' % (name, P_pad)] = wn.program_digest(planlib.uniform_program(build, mp, P_pad), mp)
+    return out
+
+
+def test_programs_reproduce_the_recorded_digests():
+    """Item table, workgroup map, reduce rules, partial-buffer size and zero-fill decision of the four networks at five
+    point counts, both program kinds: byte for byte what tests/golden/wgrad_programs.json recorded."""
+    want = json.load(open(GOLDEN))['default']
+    assert len(want) == len(PLANS) * len(DIGEST_P_PADS) * 2
+    got = program_digests(PLANS)
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], key
+
+
+def test_programs_reproduce_the_recorded_digests_without_the_narrow_slowdown():
+    """MSDF_WGRAD_ALL_NARROW_SLOW=0 (read when plan.py is imported, hence the subprocess) still switches the 30 % off: the
+    colour network's balanced programs, two of which differ from the default ones."""
+    want = json.load(open(GOLDEN))
+    assert any(want['all_narrow_slow_0'][k] != want['default'][k] for k in want['all_narrow_slow_0'])
+    code = ('import json, sys; sys.path[:0] = %r; import test_wgrad_cpu as t; '
+            'print(json.dumps(t.program_digests(["color"])))' % [p for p in sys.path if p])
+    env = dict(os.environ, MSDF_WGRAD_ALL_NARROW_SLOW='0')
+    got = json.loads(subprocess.check_output([sys.executable, '-c', code], env=env).decode().strip().splitlines()[-1])
+    for key, digest in sorted(want['all_narrow_slow_0'].items()):
+        assert got[key] == digest, key

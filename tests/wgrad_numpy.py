@@ -8,6 +8,8 @@ does not depend on the split counts: that is the property the kernels have to re
 
 Sums are formed in float64 and cast to fp32 once.  With the integer-valued operands of the exact tests every value on
 the way is an integer below 2^24, so the cast is exact and so is any fp32 summation order on the device."""
+import hashlib
+
 import numpy as np
 
 
@@ -136,13 +138,17 @@ def terms_per_rule(prog):
 
 def split_ranges(n_stages, n_splits):
     """Stage range [begin, end) of every split: the ceiling division of the item ABI, clipped (a split may be empty)."""
-    per = -(-n_stages // n_splits)
-    out = []
-    for s in range(n_splits):
-        b = s * per
-        e = min(n_stages, b + per)
-        out.append((b, max(b, e)))
-    return out
+    from monosdf_amd import plan as planlib
+    return [planlib.split_range(n_stages, n_splits, s) for s in range(n_splits)]
+
+
+def program_digest(prog, mp):
+    """What a program hands to the device, as recorded in tests/golden/wgrad_programs.json: SHA-256 of the item table,
+    the workgroup map and the reduce rules, the size of the partial buffer and the zero-fill decision.  Uses nothing
+    of a program but items_bytes / wg_map / rules_bytes / part_f / writes_every_element."""
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    return {'items': sha(prog.items_bytes()), 'wg_map': sha(prog.wg_map()), 'rules': sha(prog.rules_bytes()),
+            'part_f': int(prog.part_f), 'full': bool(prog.writes_every_element(mp.n_w + mp.n_b, mp.maps_np))}
 
 
 def headline_plans():
