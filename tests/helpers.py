@@ -109,11 +109,16 @@ def check(errlog, test, case, key, err, default=TOL):
     assert err <= tol, (test, case, key, err, tol)
 
 
-def hash_table_gradients(emb, offs, S, H, x, grad, grad2, gg, forms):
+def hash_table_gradients(emb, offs, S, H, x, grad, grad2, gg, forms, pitch=0, pad=0.0, prefill=None, guard=0):
     """The hash grid's table-gradient entry points through raw ctypes: the forward for dy_dx, then every form named in
-    `forms`, each into a fresh buffer (zeros; NaN for the "=" form 'fused_out'), returned by name.  'atomic' / 'ws':
-    msdf_hash_encode_backward / _ws of `grad` (also '<form>_inputs'); 'atomic_second' / 'ws_second': the second
-    backward of (`grad2`, gg) (also '<form>_grad'); 'fused' / 'fused_out': both terms.  Also 'dy_dx', 'workspace', 'nbytes'."""
+    `forms`, each into a fresh buffer (zeros; NaN for the "=" forms 'fused_out' and 'node'), returned by name.  'atomic' /
+    'ws': msdf_hash_encode_backward / _ws of `grad` (also '<form>_inputs'); 'atomic_second' / 'ws_second': the second
+    backward of (`grad2`, gg) (also '<form>_grad'); 'fused' / 'fused_out': both terms; 'node': msdf_hash_node_scatter,
+    both terms, "=".  Also 'dy_dx', 'workspace', 'nbytes'.
+    pitch > 0: 'node' reads its two operands as point-major rows [B, pitch] (level l, channel c at column l C + c), the
+    columns from L C on filled with `pad`.  prefill: what the "+=" forms start from instead of zeros ([n, C]; the "="
+    forms ignore it).  guard > 0: every buffer has that many rows after the table, filled with 1234.5, returned as
+    '<form>_guard' (the table itself is r[form], [n, C], as without)."""
     from monosdf_amd import _lib
     P, st = _lib.ptr, _lib.stream_ptr()
     (L, B, C), n = grad.shape, emb.shape[0]
@@ -123,8 +128,24 @@ def hash_table_gradients(emb, offs, S, H, x, grad, grad2, gg, forms):
     nbytes = _lib.load().msdf_hash_scatter_workspace_bytes(B, C, L, n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
     r = {'dy_dx': dy, 'workspace': ws, 'nbytes': nbytes}
+
+    def rows(t):                         # [L, B, C] -> [B, pitch]
+        m = torch.full((B, pitch), float(pad), device='cuda')
+        m[:, :L * C] = t.permute(1, 0, 2).reshape(B, L * C)
+        return m.contiguous()
+
     for f in forms:
-        t = r[f] = torch.full_like(emb, float('nan')) if f == 'fused_out' else torch.zeros_like(emb)
+        buf = torch.empty(n + guard, C, device='cuda')
+        if f in ('fused_out', 'node'):
+            buf[:n] = float('nan')
+        elif prefill is not None:
+            buf[:n] = prefill
+        else:
+            buf[:n] = 0.0
+        if guard:
+            buf[n:] = 1234.5
+            r[f + '_guard'] = buf[n:]
+        t = r[f] = buf[:n]
         tail = (st,) if f.startswith('atomic') else (n, P(ws), nbytes, st)
         sfx = '' if f.startswith('atomic') else '_ws'
         if f in ('atomic', 'ws'):
@@ -135,6 +156,10 @@ def hash_table_gradients(emb, offs, S, H, x, grad, grad2, gg, forms):
             ggrad = r[f + '_grad'] = torch.zeros(L, B, C, device='cuda')
             _lib.call('msdf_hash_encode_second_backward' + sfx, P(grad2), P(x), P(emb), P(offs), B, 3, C, L, S, H, 1,
                       P(dy), P(gg), P(ggrad), P(t), *tail)
+        elif f == 'node':
+            g1, g2 = (rows(grad), rows(grad2)) if pitch else (grad, grad2)
+            r['node_operands'] = (g1, g2)                 # alive until the caller has synchronised
+            _lib.call('msdf_hash_node_scatter', P(g1), P(g2), pitch, P(x), P(offs), P(t), B, C, L, S, H, P(gg), *tail)
         else:
             _lib.call('msdf_hash_encode_backward_' + f, P(grad), P(grad2), P(x), P(offs), P(t), B, 3, C, L, S, H,
                       P(gg), *tail)
