@@ -201,6 +201,16 @@ int msdf_sdf_forward_if(const msdf_plan_t* plan, const void* wpack, const float*
 int msdf_sdf_forward_lm(const msdf_plan_t* plan, const void* wpack, const float* bpack, const float* x,
                         const float* aux, int aux_C, int aux_LC, int P, float clamp_radius, float sphere_scale,
                         float* sdf, const uint32_t* run_flag, void* stream);
+/* msdf_sdf_forward_lm (bit-identical sdf) for P = rays * n_cols points, point ray * n_cols + c, that also stores the
+ * post-activation of every hidden layer of the points whose column c has col_slot[c] >= 0 (col_slot: n_cols entries on
+ * the device) to row ray * n_slots + col_slot[c] of H, laid out as the H of an msdf_sdf_fwd_grad launch with P_pad
+ * rows: the staging buffer (h_stage, stage_pad) of the launch that may then skip the hidden layers of those points
+ * (msdf_fg_args_t.n_reuse).  Sets *h_saved = 1.
+ * fp32 core only (MSDF_ERR_UNSUPPORTED otherwise). */
+int msdf_sdf_forward_save(const msdf_plan_t* plan, const void* wpack, const float* bpack, const float* x,
+                          const float* aux, int aux_C, int aux_LC, int P, float clamp_radius, float sphere_scale,
+                          float* sdf, const uint32_t* run_flag, float* H, int P_pad, const int32_t* col_slot,
+                          int n_cols, int n_slots, uint32_t* h_saved, void* stream);
 
 typedef struct {
   const void* wpack;
@@ -228,6 +238,22 @@ typedef struct {
                               msdf_hash_node_forward writes it: nrm then also holds the grid part of d sdf / d x,
                               nrm += aux_dx_scale * sum_{l,c} r_aux[l,c] dy_dx[l,.,c] (what msdf_hash_node_input_gradient
                               adds as a launch of its own; reference kernel_input_backward, hashencoder.cu:346-372) */
+  /* Evaluation order != row order (fp32 core only; the bf16 cores ignore these fields).  The point evaluated at row r
+   * of the launch grid is row row_map[r] of every tensor AND of the workspace (a permutation of [0, P) that maps
+   * [n_feat, P) and [n_clamp, P) to themselves): which workgroup evaluates a point changes, nothing that is read or
+   * written does.  NULL = identity. */
+  const int32_t* row_map;
+  /* Reuse of hidden activations that msdf_sdf_forward_save staged in h_stage (rows in evaluation order, stage_pad rows
+   * per layer block): a workgroup whose 64 evaluation rows lie below n_reuse (a multiple of 64, <= stage_pad) skips
+   * the hidden layers' forward products -- it takes the activations from the staged rows and stores them to the
+   * points' own rows of H on the way -- if and only if smp_flags[1] == 0 (the sampler stopped after its first round)
+   * and *h_saved != 0 (the save ran).  Decided on the device, per workgroup; n_reuse == 0 or a NULL pointer:
+   * everything is computed. */
+  const uint32_t* smp_flags;
+  const uint32_t* h_saved;
+  int32_t n_reuse;
+  int32_t stage_pad;
+  const float* h_stage;
 } msdf_fg_args_t;
 int msdf_sdf_fwd_grad(const msdf_plan_t* plan, const msdf_fg_args_t* args, void* stream);
 
@@ -265,6 +291,8 @@ typedef struct {
   float* gg_out;           /* with dy_dx: [P,3] <- aux_dx_scale * g_nrm (the scatter's grad_grad_inputs), or NULL */
   float aux_dx_scale;
   int32_t pad_;
+  const int32_t* row_map;  /* as in msdf_fg_args_t (the same map as the forward + gradient launch, or NULL): grid row r
+                              works on row row_map[r] of every tensor and of the workspace */
 } msdf_bw_args_t;
 int msdf_sdf_backward(const msdf_plan_t* plan, const msdf_bw_args_t* args, void* stream);
 
@@ -447,6 +475,12 @@ typedef struct {
   int32_t eik_unit;          /* 1: eik_uniform holds U[0,1) values, mapped to (2u - 1) * bound here (reference:
                                 uniform_(-R, R), network.py:587); 0: it holds the points themselves */
   int32_t pad_;
+  int32_t* row_map;          /* [N * S (+ 4 N)] or NULL: msdf_sampler_finish writes the evaluation order of the SDF
+                                kernels (msdf_fg_args_t.row_map): evaluation rows [0, n_extra N) are the dense-set
+                                columns, row ray * n_extra + e for extra_idx entry e, rows [n_extra N, S N) the other
+                                samples of each ray in sorted order, the eikonal rows map to themselves;
+                                row_map[r] = the row of pts_out / z_out that evaluation row r is */
+  uint32_t* h_saved;         /* [1] or NULL: zeroed by msdf_sampler_init (msdf_sdf_forward_save sets it) */
 } msdf_sampler_args_t;
 int msdf_sampler_init(const msdf_sampler_args_t* args, void* stream);
 int msdf_sampler_beta(const msdf_sampler_args_t* args, void* stream);

@@ -55,7 +55,8 @@ class FgArgs(C.Structure):
                 ('clamp_radius', C.c_float), ('sphere_scale', C.c_float),
                 ('sdf', _P), ('feat', _P), ('nrm', _P), ('r_aux', _P), ('clamped', _P),
                 ('H', _P), ('PM', _P), ('IN0', _P), ('save', C.c_int32), ('aux_C', C.c_int32), ('aux_LC', C.c_int32),
-                ('aux_dx_scale', C.c_float), ('dy_dx', _P)]
+                ('aux_dx_scale', C.c_float), ('dy_dx', _P),
+                ('row_map', _P), ('smp_flags', _P), ('h_saved', _P), ('n_reuse', C.c_int32), ('stage_pad', C.c_int32), ('h_stage', _P)]
 
 
 class BwArgs(C.Structure):
@@ -64,7 +65,8 @@ class BwArgs(C.Structure):
                 ('g_sdf', _P), ('g_feat', _P), ('g_nrm', _P), ('g_raux', _P), ('clamped', _P),
                 ('H', _P), ('PM', _P), ('QB', _P), ('T', _P), ('AB', _P), ('GSDF', _P), ('QLAST', _P),
                 ('g_aux', _P), ('g_sdf_b', _P), ('g_nrm_b', _P), ('aux_C', C.c_int32), ('aux_LC', C.c_int32),
-                ('dy_dx', _P), ('gg_out', _P), ('aux_dx_scale', C.c_float), ('pad_', C.c_int32)]
+                ('dy_dx', _P), ('gg_out', _P), ('aux_dx_scale', C.c_float), ('pad_', C.c_int32),
+                ('row_map', _P)]
 
 
 class ColorFwdArgs(C.Structure):
@@ -128,7 +130,7 @@ class SamplerArgs(C.Structure):
                 ('extra_idx', _P), ('eik_idx', _P), ('z_out', _P), ('z_eik', _P), ('pts_out', _P),
                 ('eik_uniform', _P), ('nei_rand', _P), ('far_out', _P), ('rounds_out', _P),
                 ('dbg_dstar', _P), ('dbg_err0', _P), ('dbg_cdf', _P), ('eik_u', _P), ('eik_unit', C.c_int32),
-                ('pad_', C.c_int32)]
+                ('pad_', C.c_int32), ('row_map', _P), ('h_saved', _P)]
 
 
 _ERR = {1: 'invalid argument', 2: 'kernel launch failed', 3: 'unsupported configuration'}
@@ -166,6 +168,8 @@ _SIGNATURES = {
     'msdf_sdf_forward': [C.POINTER(Plan), _P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P],
     'msdf_sdf_forward_if': [C.POINTER(Plan), _P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P],
     'msdf_sdf_forward_lm': [C.POINTER(Plan), _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P],
+    'msdf_sdf_forward_save': [C.POINTER(Plan), _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P,
+                              _P, C.c_int, _P, C.c_int, C.c_int, _P, _P],
     'msdf_sdf_fwd_grad': [C.POINTER(Plan), C.POINTER(FgArgs), _P],
     'msdf_sdf_backward': [C.POINTER(Plan), C.POINTER(BwArgs), _P],
     'msdf_color_forward': [C.POINTER(Plan), C.POINTER(ColorFwdArgs), _P],

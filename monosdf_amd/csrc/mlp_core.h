@@ -366,6 +366,10 @@ struct CoreF32 {
 #define MLP_F32_AUX_LEVEL_MAJOR true     // timing experiments build a variant with false (rows + transposes, round 3's kernels)
 #endif
   static constexpr bool AUX_LEVEL_MAJOR = MLP_F32_AUX_LEVEL_MAJOR;
+  // the SDF kernels may evaluate their points in another order than the caller's tensors hold them (msdf_fg_args_t.row_map)
+  // and reuse hidden activations the sampler's forward kernel saved; compiled out of the bf16 cores, whose kernels sit
+  // at the register limit
+  static constexpr bool ROW_MAP = true;
   static __device__ __forceinline__ float softplus(const float a) {
     float h, s;
     softplus100(a, h, s);

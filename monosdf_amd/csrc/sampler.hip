@@ -63,6 +63,7 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_init_k(const SmpArgs a) {
   // the round flags start at zero: no launch of this call reads them before the round kernels behind this one
   if (ray == 0 && a.flags != nullptr)
     for (int i = lane; i < 2 * a.max_rounds; i += 64) a.flags[i] = 0u;
+  if (ray == 0 && lane == 0 && a.h_saved != nullptr) a.h_saved[0] = 0u;     // set by msdf_sdf_forward_save, if it runs
   const int n = a.n_eval;
   const float o0 = a.ray_o[ray * 3 + 0], o1 = a.ray_o[ray * 3 + 1], o2 = a.ray_o[ray * 3 + 2];
   const float d0 = a.ray_d[ray * 3 + 0], d1 = a.ray_d[ray * 3 + 1], d2 = a.ray_d[ray * 3 + 2];
@@ -360,6 +361,10 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
     else if (j == a.n_final) x = a.near;
     else if (j == a.n_final + 1) x = a.far;
     else x = zrow[min((int)extra[j - a.n_final - 2], rounds * a.n_eval - 1)];
+    // When the last enqueued round asked for another one, final_z was never written (the caller discards the pass):
+    // whatever the memory holds must still rank as a permutation, which counting with < does only without NaNs.
+    // row_map is an index table: a position nobody wrote would send the SDF kernels anywhere.
+    if (x != x) x = INFINITY;
     v[j] = x;
   }
   smp_sync();
@@ -367,10 +372,23 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
   const float d0 = a.ray_d[ray * 3 + 0], d1 = a.ray_d[ray * 3 + 1], d2 = a.ray_d[ray * 3 + 2];
   for (int j = lane; j < S; j += 64) {
     const float x = v[j];
-    int r = 0;
-    for (int k = 0; k < S; ++k) r += (v[k] < x || (v[k] == x && k < j)) ? 1 : 0;
+    // rn: the rank among the samples that are not dense-set columns (the first n_final + 2 entries of v)
+    int r = 0, rn = 0;
+    for (int k = 0; k < S; ++k) {
+      const int before = (v[k] < x || (v[k] == x && k < j)) ? 1 : 0;
+      r += before;
+      rn += (k < a.n_final + 2) ? before : 0;
+    }
     sorted[r] = x;
     a.z_out[(size_t)ray * S + r] = x;
+    if (a.row_map != nullptr) {
+      // evaluation order of the SDF kernels: the dense-set columns of all rays first (a ray's columns in extra_idx
+      // order: whole wave tiles of points the sampler's first round evaluated), then the other samples ray by ray,
+      // sorted; this sample is row ray * S + r of the outputs
+      const int e = j - a.n_final - 2;
+      const int er = (e >= 0) ? ray * a.n_extra + e : a.N * a.n_extra + ray * (S - a.n_extra) + rn;
+      a.row_map[er] = ray * S + r;
+    }
     if (a.pts_out != nullptr) {
       float* p = a.pts_out + ((size_t)ray * S + r) * 3;
       p[0] = o0 + x * d0; p[1] = o1 + x * d1; p[2] = o2 + x * d2;
@@ -385,6 +403,8 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
     if (a.pts_out != nullptr && a.eik_uniform != nullptr) {
       // eikonal block (reference network.py:583-594): [uniform | near-surface | their jittered neighbours]
       float* e = a.pts_out + (size_t)a.N * S * 3;
+      if (a.row_map != nullptr)      // the eikonal block is evaluated where it stands
+        for (int i = 0; i < 4; ++i) a.row_map[a.N * S + i * a.N + ray] = a.N * S + i * a.N + ray;
       const float od[3] = {o0 + ze * d0, o1 + ze * d1, o2 + ze * d2};
 #pragma unroll
       for (int c = 0; c < 3; ++c) {

@@ -15,14 +15,32 @@ struct PointCtx {
   float x0, x1, x2;
 };
 
+// The row of the workgroup's grid this lane's point sits at: the EVALUATION row.  Without a row map it is also the row
+// of the point in every tensor.
 template <class Core>
-__device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, const int P) {
+__device__ __forceinline__ int eval_row() {
+  return blockIdx.x * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane_id() & 15);
+}
+
+// row_map (cores with ROW_MAP): the point evaluated at row r of the grid is row row_map[r] of the caller's tensors AND
+// of the workspace -- pt / ptc are that row from here on, so nothing below knows about the order of evaluation, and
+// the workspace holds what it holds without a map (the weight-gradient kernels sum its rows in the same order).  An
+// entry outside [0, P) (a map nobody filled) falls back to the row itself: never an address outside the tensors.
+template <class Core>
+__device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, const int P,
+                                               const int32_t* __restrict__ row_map = nullptr) {
   PointCtx c;
   const int lane = lane_id();
-  const int wave = threadIdx.x >> 6;
-  c.pt = blockIdx.x * Core::PTS_PER_WG + wave * MLP_PTS_PER_WAVE + (lane & 15);
-  c.valid = c.pt < P;
-  c.ptc = c.valid ? c.pt : (P - 1);
+  const int pe = eval_row<Core>();
+  c.valid = pe < P;
+  c.ptc = c.valid ? pe : (P - 1);
+  if constexpr (Core::ROW_MAP) {
+    if (row_map != nullptr) {
+      const int m = row_map[c.ptc];
+      if ((unsigned)m < (unsigned)P) c.ptc = m;
+    }
+  }
+  c.pt = c.valid ? c.ptc : pe;      // the padded tail keeps its own workspace rows
   c.q = lane >> 4;
   c.x0 = x[(size_t)c.ptc * 3 + 0];
   c.x1 = x[(size_t)c.ptc * 3 + 1];
@@ -190,6 +208,27 @@ struct SoftplusSaveHooks {
   __device__ __forceinline__ void drain() { st.issue(); }
 };
 
+// the same with the store decided per lane (on == false: a lane whose point is not saved): the sampler's forward kernel
+// saving the rows the forward + gradient kernel will reuse
+template <class Core>
+struct SoftplusSaveLaneHooks {
+  PendingStores st;
+  bool on;
+  __device__ __forceinline__ SoftplusSaveLaneHooks(float* H) : on(H != nullptr) { st.dst = H; st.n = 0; st.t0 = 0; }
+  __device__ __forceinline__ void pre(const int, const int) { if (on) st.issue(); else st.n = 0; }
+  __device__ __forceinline__ void post(const int o0, const int, const bool pair, v4f& a0, v4f& a1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a0[r] = Core::softplus(a0[r]);
+    st.s0 = a0; st.t0 = o0; st.n = 1;
+    if (pair) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a1[r] = Core::softplus(a1[r]);
+      st.s1 = a1; st.n = 2;
+    }
+  }
+  __device__ __forceinline__ void drain() { if (on) st.issue(); else st.n = 0; }
+};
+
 // gradient sweep of the fwd+grad kernel: g -> p = s g with s = 1 - exp(-100 h), h loaded from H; p saved to PM.
 // Tiles >= ot (the input block behind a skip layer's hidden tiles; ot == 0: no epilogue at all) are left alone.
 struct GradSweepHooks {
@@ -213,6 +252,42 @@ struct GradSweepHooks {
       for (int r = 0; r < 4; ++r) a0[r] = (1.0f - one_minus_sigmoid_from_h(h0[r])) * a0[r];
       st.s0 = a0; st.t0 = o0; st.n = save ? 1 : 0;
       if (pair && o1 < ot) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a1[r] = (1.0f - one_minus_sigmoid_from_h(h1[r])) * a1[r];
+        st.s1 = a1; st.n = save ? 2 : 0;
+      }
+    }
+  }
+  __device__ __forceinline__ void drain() { st.issue(); }
+};
+
+// The same for a workgroup that reuses the hidden activations the sampler's forward kernel staged (HS, rows in
+// evaluation order): h comes from the staged row and is stored to the point's own row of H on the way -- the loads
+// replace the sweep's own loads of H, the stores are the ones the forward chain would have issued.
+struct GradSweepCopyHooks {
+  const float* HS;
+  float* H;
+  int ot;
+  bool save;
+  v4f h0, h1;
+  PendingStores st;
+  __device__ __forceinline__ GradSweepCopyHooks(const float* HS_, float* H_, float* PM, const int ot_, const bool save_)
+      : HS(HS_), H(H_), ot(ot_), save(save_) { st.dst = PM; st.n = 0; st.t0 = 0; }
+  __device__ __forceinline__ void pre(const int o0, const int o1) {
+    st.issue();
+    if (ot > 0) {
+      h0 = *(const v4f*)(HS + 16 * (o0 < ot ? o0 : ot - 1));
+      h1 = *(const v4f*)(HS + 16 * (o1 < ot ? o1 : ot - 1));
+    }
+  }
+  __device__ __forceinline__ void post(const int o0, const int o1, const bool pair, v4f& a0, v4f& a1) {
+    if (o0 < ot) {
+      *(v4f*)(H + 16 * o0) = h0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a0[r] = (1.0f - one_minus_sigmoid_from_h(h0[r])) * a0[r];
+      st.s0 = a0; st.t0 = o0; st.n = save ? 1 : 0;
+      if (pair && o1 < ot) {
+        *(v4f*)(H + 16 * o1) = h1;
 #pragma unroll
         for (int r = 0; r < 4; ++r) a1[r] = (1.0f - one_minus_sigmoid_from_h(h1[r])) * a1[r];
         st.s1 = a1; st.n = save ? 2 : 0;
@@ -295,13 +370,29 @@ struct SweepDownHooks {
 // ---------------------------------------------------------------------------
 // F: forward only, sdf only (get_sdf_vals; reference network.py:131-137 / 307-309)
 // ---------------------------------------------------------------------------
-template <class Core>
+// SAVE: also store the hidden post-activations of the points in the columns col_slot names (msdf_sdf_forward_save) to
+// the rows of H that the forward + gradient launch of the same step evaluates them at; the arithmetic is the same
+struct HSaveArgs {
+  float* H;                   // the H of an msdf_sdf_fwd_grad launch with P_pad rows
+  int P_pad;
+  const int32_t* col_slot;    // [n_cols]: slot of a column, or -1
+  int n_cols, n_slots;        // point ray * n_cols + c goes to row ray * n_slots + col_slot[c]
+};
+
+template <class Core, bool SAVE = false>
 __device__ __forceinline__ void sdf_forward_body(const msdf_plan_t& plan, const typename Core::wvec* __restrict__ wpack,
                                                  const float* __restrict__ bpack, const float* __restrict__ x,
                                                  const float* __restrict__ aux, const AuxView av, const int P,
                                                  const float clamp_radius, const float sphere_scale,
-                                                 float* __restrict__ sdf_out, void* lds) {
+                                                 float* __restrict__ sdf_out, void* lds,
+                                                 const HSaveArgs hs = HSaveArgs()) {
   const PointCtx c = load_point<Core>(x, P);
+  int srow = -1;              // row of H this lane's point is saved to
+  if constexpr (SAVE) {
+    const int ray = c.ptc / hs.n_cols;      // (no row map here: ptc is the point index)
+    const int slot = hs.col_slot[c.ptc - ray * hs.n_cols];
+    if (c.valid && slot >= 0 && slot < hs.n_slots) srow = ray * hs.n_slots + slot;
+  }
   v4f in[MT], acc[MT];
   const int in0_tiles = plan.e_tiles + plan.aux_tiles;
   {
@@ -318,7 +409,12 @@ __device__ __forceinline__ void sdf_forward_body(const msdf_plan_t& plan, const 
       load_input_tiles<Core::AUX_LEVEL_MAJOR>(in0, plan, aux, av, c);
       place_tiles(in, L.skip_tile, in0, in0_tiles);
     }
-    if constexpr (Core::BIAS_IN_HOOKS) {
+    if constexpr (SAVE) {
+      static_assert(!SAVE || Core::BIAS_IN_HOOKS, "the save kernel exists for the fp32 core");
+      float* Hl = (srow >= 0) ? hs.H + (size_t)L.hpre * hs.P_pad + (size_t)srow * (16 * L.ot) + 4 * c.q : nullptr;
+      Core::gemm_bias(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusSaveLaneHooks<Core>(Hl),
+                      bpack + L.bias_off + 4 * c.q);
+    } else if constexpr (Core::BIAS_IN_HOOKS) {
       Core::gemm_bias(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusHooks<Core>(), bpack + L.bias_off + 4 * c.q);
     } else {
       load_bias(acc, bpack + L.bias_off, L.ot, c.q);
@@ -341,10 +437,25 @@ __device__ __forceinline__ void sdf_forward_body(const msdf_plan_t& plan, const 
 // ---------------------------------------------------------------------------
 typedef msdf_fg_args_t FgArgs;
 
+// Whether this workgroup's evaluation rows are points whose hidden activations the sampler's forward kernel staged
+// (msdf_sdf_forward_save), so that the forward chain can be skipped.  Decided here, on the device: only if the sampler
+// stopped after its first round are these rows the points that kernel evaluated.  Workgroup-uniform (two scalar loads).
 template <class Core>
+__device__ __forceinline__ bool sdf_fwd_grad_reuses(const msdf_plan_t& plan, const FgArgs& a) {
+  if constexpr (Core::ROW_MAP) {
+    if ((int)((blockIdx.x + 1) * Core::PTS_PER_WG) <= a.n_reuse && plan.n_layers >= 2 && a.smp_flags != nullptr &&
+        a.h_saved != nullptr && a.h_stage != nullptr)
+      return a.smp_flags[1] == 0u && a.h_saved[0] != 0u;
+  }
+  return false;
+}
+
+// REUSE: the body of a workgroup for which sdf_fwd_grad_reuses() holds -- a body of its own rather than a branch around
+// the forward chain, which cost the common path 94 spilled registers
+template <class Core, bool REUSE = false>
 __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const FgArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  const PointCtx c = load_point<Core>(a.x, a.P);
+  const PointCtx c = load_point<Core>(a.x, a.P, a.row_map);
   const AuxView av = {a.aux_C, a.aux_LC, a.P};
   v4f in[MT], acc[MT];
   const int nl = plan.n_layers;
@@ -363,8 +474,23 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
   // workgroup-uniform on purpose: the gemm below contains barriers and cooperative weight staging
   const bool want_feat = (int)(blockIdx.x * Core::PTS_PER_WG) < a.n_feat;
 
+  // the point's staged row of layer L (REUSE): evaluation order, stage_pad rows per layer block
+  auto srow = [&](const msdf_layer_t& L) {
+    return (size_t)L.hpre * (size_t)a.stage_pad + (size_t)eval_row<Core>() * (16 * L.ot) + 4 * c.q;
+  };
   // ---------------- forward chain ----------------
-  for (int l = 0; l < nl - 1; ++l) {
+  if constexpr (REUSE) {
+    // the last hidden activation as the sampler's forward kernel computed and staged it
+    const msdf_layer_t L = plan.layer[nl - 2];
+    const float* Hs = a.h_stage + srow(L);
+    const int otl = L.ot - 1;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const v4f h = *(const v4f*)(Hs + 16 * (t < otl ? t : otl));
+      in[t] = (t < L.ot) ? h : V4ZERO;
+    }
+  }
+  for (int l = 0; l < (REUSE ? 0 : nl - 1); ++l) {
     const msdf_layer_t L = plan.layer[l];
     if (L.skip_tile >= 0) {
       v4f in0[5];
@@ -434,7 +560,7 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     // p of the last hidden layer: no product precedes it (g is the sdf row itself) -- every H load before
     // the first PM store, tile index clamped instead of guarded, so that no branch separates the loads
     const msdf_layer_t L = plan.layer[nl - 2];
-    const float* Hl = a.H + row(L);
+    const float* Hl = REUSE ? a.h_stage + srow(L) : a.H + row(L);
     float* Pl = a.PM + row(L);
     const int otl = L.ot - 1;
     v4f hh[MT];
@@ -443,6 +569,7 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       if (t == 0 || t < L.ot) {
+        if constexpr (REUSE) *(v4f*)(a.H + row(L) + 16 * t) = hh[t];      // the staged row becomes the point's row of H
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[t][r] = (1.0f - one_minus_sigmoid_from_h(hh[t][r])) * acc[t][r];
         if (a.save) *(v4f*)(Pl + 16 * t) = acc[t];
@@ -457,8 +584,13 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     for (int t = 0; t < MT; ++t) in[t] = (t < L.ot) ? acc[t] : V4ZERO;
     zero_tiles(acc);
     const msdf_layer_t Lp = plan.layer[l > 0 ? l - 1 : 0];
-    Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
-               GradSweepHooks(a.H + row(Lp), a.PM + row(Lp), l > 0 ? Lp.ot : 0, a.save != 0));
+    if constexpr (REUSE) {
+      Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
+                 GradSweepCopyHooks(a.h_stage + srow(Lp), a.H + row(Lp), a.PM + row(Lp), l > 0 ? Lp.ot : 0, a.save != 0));
+    } else {
+      Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
+                 GradSweepHooks(a.H + row(Lp), a.PM + row(Lp), l > 0 ? Lp.ot : 0, a.save != 0));
+    }
     if (l == 0) take_input_grad(0);
     else if (L.skip_tile >= 0) take_input_grad(L.skip_tile);
   }
@@ -535,7 +667,7 @@ __device__ __forceinline__ void load_rbar(v4f (&rbar)[5], const msdf_plan_t& pla
 template <class Core>
 __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const BwArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  const PointCtx c = load_point<Core>(a.x, a.P);
+  const PointCtx c = load_point<Core>(a.x, a.P, a.row_map);
   const int nl = plan.n_layers;
   const size_t Pp = (size_t)a.P_pad;
   const bool live = c.valid && !(a.clamped != nullptr && a.clamped[c.ptc]);

@@ -66,10 +66,23 @@ msdf_sdf_forward_k(const msdf_plan_t plan, const v4f* __restrict__ wpack, const 
   sdf_forward_body<CoreF32>(plan, wpack, bpack, x, aux, av, P, clamp_radius, sphere_scale, sdf_out, lds);
 }
 
+// the same values, and the hidden activations of the dense-set columns saved for the forward + gradient kernel
+__global__ void __launch_bounds__(CoreF32::THREADS, CoreF32::WGS_PER_CU)
+msdf_sdf_forward_save_k(const msdf_plan_t plan, const v4f* __restrict__ wpack, const float* __restrict__ bpack,
+                        const float* __restrict__ x, const float* __restrict__ aux, const AuxView av, const int P,
+                        const float clamp_radius, const float sphere_scale, float* __restrict__ sdf_out,
+                        const uint32_t* __restrict__ run_flag, const HSaveArgs hs, uint32_t* __restrict__ h_saved) {
+  extern __shared__ v4f lds[];
+  if (run_flag != nullptr && *run_flag == 0u) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *h_saved = 1u;
+  sdf_forward_body<CoreF32, true>(plan, wpack, bpack, x, aux, av, P, clamp_radius, sphere_scale, sdf_out, lds, hs);
+}
+
 __global__ void __launch_bounds__(CoreF32::THREADS, CoreF32::WGS_PER_CU)
 msdf_sdf_fwd_grad_k(const msdf_plan_t plan, const FgArgs a) {
   extern __shared__ v4f lds[];
-  sdf_fwd_grad_body<CoreF32>(plan, a, lds);
+  if (sdf_fwd_grad_reuses<CoreF32>(plan, a)) sdf_fwd_grad_body<CoreF32, true>(plan, a, lds);
+  else sdf_fwd_grad_body<CoreF32>(plan, a, lds);
 }
 
 __global__ void __launch_bounds__(CoreF32::THREADS, CoreF32::WGS_PER_CU)
@@ -129,6 +142,27 @@ extern "C" int msdf_sdf_forward_lm(const msdf_plan_t* plan, const void* wpack, c
   });
 }
 
+extern "C" int msdf_sdf_forward_save(const msdf_plan_t* plan, const void* wpack, const float* bpack, const float* x,
+                                     const float* aux, int aux_C, int aux_LC, int P, float clamp_radius,
+                                     float sphere_scale, float* sdf, const uint32_t* run_flag, float* H, int P_pad,
+                                     const int32_t* col_slot, int n_cols, int n_slots, uint32_t* h_saved,
+                                     void* stream) {
+  if (plan == nullptr || P < 0 || H == nullptr || col_slot == nullptr || h_saved == nullptr) return MSDF_ERR_ARG;
+  if (plan->precision != MSDF_PRECISION_F32) return MSDF_ERR_UNSUPPORTED;
+  // every saved row ray * n_slots + slot (slot < n_slots) lies inside the P_pad rows of H
+  if (n_cols < 1 || n_slots < 1 || n_slots > n_cols || (P % n_cols) != 0 || !padded_ok(0, P_pad) ||
+      (int64_t)(P / n_cols) * n_slots > (int64_t)P_pad)
+    return MSDF_ERR_ARG;
+  if (P == 0) return MSDF_OK;
+  if (plan->aux_tiles > 0 && aux == nullptr) return MSDF_ERR_ARG;
+  if (!aux_layout_ok(plan, aux_C, aux_LC)) return MSDF_ERR_ARG;
+  const AuxView av = {aux_C, aux_LC, P};
+  const HSaveArgs hs = {H, P_pad, col_slot, n_cols, n_slots};
+  return mlp_launch<CoreF32>(msdf_sdf_forward_save_k, (P + CoreF32::PTS_PER_WG - 1) / CoreF32::PTS_PER_WG, stream, *plan,
+                             (const v4f*)wpack, bpack, x, aux, av, P, clamp_radius, sphere_scale, sdf, run_flag, hs,
+                             h_saved);
+}
+
 extern "C" int msdf_sdf_forward_if(const msdf_plan_t* plan, const void* wpack, const float* bpack, const float* x,
                                    const float* aux, int P, float clamp_radius, float sphere_scale, float* sdf,
                                    const uint32_t* run_flag, void* stream) {
@@ -148,6 +182,12 @@ extern "C" int msdf_sdf_fwd_grad(const msdf_plan_t* plan, const msdf_fg_args_t* 
   if (plan->aux_tiles > 0 && a->aux == nullptr) return MSDF_ERR_ARG;
   if (!aux_layout_ok(plan, a->aux_C, a->aux_LC)) return MSDF_ERR_ARG;
   if (a->dy_dx != nullptr && (a->aux_C != 2 || a->r_aux == nullptr)) return MSDF_ERR_ARG;
+  // reused rows are whole workgroups of ray samples: below the rows without features (the eikonal block, which the row
+  // map leaves in place -- what keeps the kernel's workgroup-uniform feature test valid in evaluation order)
+  if (a->n_reuse < 0 || (a->n_reuse % CoreF32::PTS_PER_WG) != 0 || a->n_reuse > a->P) return MSDF_ERR_ARG;
+  if (a->n_reuse > 0 && (a->row_map == nullptr || a->n_reuse > a->n_feat || a->h_stage == nullptr ||
+                         a->stage_pad < a->n_reuse))
+    return MSDF_ERR_ARG;
   return mlp_with_core(plan, [&](auto core) {
     typedef decltype(core) Core;
     if (!Core::AUX_LEVEL_MAJOR && (a->aux_C != 0 || a->dy_dx != nullptr)) return MSDF_ERR_UNSUPPORTED;

@@ -144,10 +144,11 @@ class _SdfBase(_FusedNet):
                                       self.feature_vector_size)
 
     # -- one fused evaluation -------------------------------------------------------------
-    def evaluate(self, x, n_clamp, n_feat, save=None, split=None):
+    def evaluate(self, x, n_clamp, n_feat, save=None, split=None, reuse=None):
         """sdf [P,1], feat [n_feat,F], d sdf/dx [P,3] for the points x; the first n_clamp points get the
         bounding-sphere clamp, the first n_feat points get feature vectors.
-        split = s: returns (sdf [:s], feat, d sdf/dx [:s], d sdf/dx [s:]) as separate tensors."""
+        split = s: returns (sdf [:s], feat, d sdf/dx [:s], d sdf/dx [s:]) as separate tensors.
+        reuse: the ops.SdfReuse of this pass (sdf_reuse()), or None."""
         if save is None:
             save = torch.is_grad_enabled()
         x = x.detach()
@@ -168,7 +169,7 @@ class _SdfBase(_FusedNet):
         radius = self.sdf_bounding_sphere if self.clamps else 0.0
         sdf, _, feat, nrm, nrm_b, r_aux = ops.SdfMlpFunction.apply(
             x, aux, flat_w, flat_b, wpack, bpack, fused, int(n_clamp), int(n_feat), radius, self.sphere_scale,
-            bool(save), ns)
+            bool(save), ns, reuse)
         if self.aux_active:
             # chain rule through x01 = (x / divide_factor + 1) / 2
             r_aux = r_aux[:, :self.aux_cols]
@@ -206,8 +207,23 @@ class _SdfBase(_FusedNet):
         with torch.no_grad():
             return self._sdf_only(x, clamp=False)[:, 0]
 
-    def _sdf_only(self, x, run_flag=None, clamp=True):
+    def sdf_reuse(self, device, N, S, n_extra, n_eik, save):
+        """The ops.SdfReuse of a pass over N rays (S samples each, n_extra of them dense-set columns, n_eik eikonal
+        points), or None where the SDF node keeps the order of its input: the bf16 cores, a hash grid in front."""
+        fused = self.packed(device)[0]
+        if fused.precision != 'fp32' or self.aux_active or N <= 0 or n_extra <= 0:
+            return None
+        return ops.SdfReuse(fused, N, S, n_extra, n_eik, save, device)
+
+    def _sdf_only(self, x, run_flag=None, clamp=True, save_for=None):
+        """save_for = (SdfReuse, col_slot, n_cols): also leave the hidden activations of the dense-set columns in the
+        SDF node's workspace (the sampler's first round)."""
         fused, _, _, wpack, bpack = self.packed(x.device)
+        if save_for is not None:
+            reuse, col_slot, n_cols = save_for
+            radius = self.sdf_bounding_sphere if (self.clamps and clamp) else 0.0
+            return ops.sdf_forward_save(fused, wpack, bpack, x.detach(), radius, self.sphere_scale, run_flag, reuse,
+                                        col_slot, n_cols)
         aux, aux_lm = None, None
         if self.aux_active:
             enc = self.encoding
@@ -430,14 +446,19 @@ class MonoSDFNetwork(nn.Module):
             guess = 0 if not mode else (K if mode == 'all' else min(K, self.ray_sampler.guess_rounds()))
             for attempt in (guess, K if guess else 0):
                 # the sampler's last kernel also writes the sample points and (training) the eikonal points
+                # the SDF node's workspace and evaluation order, shared with the sampler (fp32 core: ops.SdfReuse)
+                smp = self.ray_sampler
+                reuse = net.sdf_reuse(device, ray_dirs.shape[0], smp.N_samples + smp.N_samples_extra + 2,
+                                      smp.N_samples_extra, 4 * ray_dirs.shape[0] if self.training else 0,
+                                      torch.is_grad_enabled())
                 z_vals, z_samples_eik, x_all = self.ray_sampler.sample(ray_dirs, cam_loc, self, speculate=attempt,
-                                                                      beta0=beta)
+                                                                      beta0=beta, sdf_reuse=reuse)
                 N, S = z_vals.shape
                 P = N * S
                 points_flat = x_all[:P]
                 # one fused evaluation for the ray samples (clamped, with features) and the eikonal points
                 sdf, feature_vectors, gradients_sdf, grad_eik = net.evaluate(x_all, P, P, save=torch.is_grad_enabled(),
-                                                                                split=P)
+                                                                                split=P, reuse=reuse)
                 rgb_flat = self.rendering_network(points_flat, gradients_sdf, ray_dirs, feature_vectors, indices,
                                                   if_pixel_input=if_pixel_input, samples_per_ray=S)['rgb']
                 rgb = rgb_flat.reshape(-1, S, 3)

@@ -116,28 +116,50 @@ class ErrorBoundSampler(RaySampler):
         return out
 
     # -- the columns of the dense sample set that join the final set (ray_sampler.py:242-247) ------------------
-    def _extra_columns(self, training, noise, dev):
-        """[max_total_iters, N_samples_extra] int64 on the device: row k-1 is used when k rounds ran.  Training:
-        a random subset per size, drawn on the CPU generator as the reference does; eval: its linspace."""
+    @staticmethod
+    def column_slots(row0, n_eval):
+        """The inverse of the first row of the extra_idx table: [n_eval] int32, entry c = the position of column c
+        in row0, -1 for a column that is not in it.  None when row0 is not a set of distinct columns of the first
+        round (then its points are not one saved row each)."""
+        row0 = row0.reshape(-1).to(torch.int64)
+        n = row0.numel()
+        if n == 0 or int(row0.min()) < 0 or int(row0.max()) >= n_eval or torch.unique(row0).numel() != n:
+            return None
+        slots = torch.full((n_eval,), -1, dtype=torch.int32)
+        slots[row0] = torch.arange(n, dtype=torch.int32)
+        return slots
+
+    def _extra_columns(self, training, noise, dev, want_slots=False):
+        """(columns, slots).  columns: [max_total_iters, N_samples_extra] int64 on the device, row k-1 is used when k
+        rounds ran.  Training: a random subset per size, drawn on the CPU generator as the reference does; eval: its
+        linspace.  slots (want_slots): column_slots() of row 0 on the device, or None."""
         n_extra, n_eval, K = self.N_samples_extra, self.N_samples_eval, self.max_total_iters
         if n_extra <= 0:
-            return torch.zeros(K, 1, device=dev, dtype=torch.int64)
+            return torch.zeros(K, 1, device=dev, dtype=torch.int64), None
         if training:
             given = noise.get('extra_idx')
             if given is not None:
                 given = given.to(device=dev, dtype=torch.int64)
-                if given.dim() == 2:   # a test's table, one row per possible size
-                    return given.contiguous()
-                # a test's draw for the size the loop will end with: the same row for all sizes
-                return given.reshape(1, n_extra).expand(K, n_extra).contiguous()
-            host = torch.empty(K, n_extra, dtype=torch.int64, pin_memory=True)
+                # a test's table, one row per possible size, or its draw for the size the loop will end with: the
+                # same row for all sizes
+                table = given.contiguous() if given.dim() == 2 else \
+                    given.reshape(1, n_extra).expand(K, n_extra).contiguous()
+                slots = self.column_slots(table[0].cpu(), n_eval) if want_slots else None
+                return table, (slots.to(dev) if slots is not None else None)
+            # the table and its slots in one pinned buffer: one copy to the device
+            words = K * n_extra + (n_eval + 1) // 2
+            host = torch.empty(words, dtype=torch.int64, pin_memory=True)
+            table = host[:K * n_extra].view(K, n_extra)
             for k in range(K):
-                host[k] = torch.randperm(n_eval * (k + 1))[:n_extra]
-            return host.to(dev, non_blocking=True)
+                table[k] = torch.randperm(n_eval * (k + 1))[:n_extra]
+            host[K * n_extra:].view(torch.int32)[:n_eval] = self.column_slots(table[0], n_eval)
+            on_dev = host.to(dev, non_blocking=True)
+            return on_dev[:K * n_extra].view(K, n_extra), on_dev[K * n_extra:].view(torch.int32)[:n_eval]
         key = (str(dev), n_eval, K, n_extra)
         if key not in self._eval_columns:
             rows = [torch.linspace(0, n_eval * (k + 1) - 1, n_extra).long() for k in range(K)]
-            self._eval_columns[key] = torch.stack(rows).to(dev)
+            slots = self.column_slots(rows[0], n_eval)
+            self._eval_columns[key] = (torch.stack(rows).to(dev), slots.to(dev) if slots is not None else None)
         return self._eval_columns[key]
 
     @property
@@ -196,14 +218,19 @@ class ErrorBoundSampler(RaySampler):
             return self.max_total_iters
         return max(self._hist[which]) if self._hist[which] else 1
 
-    def sample(self, ray_dirs, cam_loc, model, want_points=True, speculate=0, beta0=None):
+    def sample(self, ray_dirs, cam_loc, model, want_points=True, speculate=0, beta0=None, sdf_reuse=None):
         """get_z_vals plus (optionally) the 3-D points of the ray samples and, in training, the eikonal
         points appended behind them -- written by the finish kernel instead of ~15 small tensor ops.
 
         speculate = k > 0: enqueue exactly k rounds WITHOUT reading the batch-global convergence flag back (the
         one host sync per round, during which the GPU would drain); rounds beyond the ones the flags ask for do
         nothing.  The caller enqueues the rest of its work and then calls confirm(), which tells whether k was
-        enough."""
+        enough.
+
+        sdf_reuse: the ops.SdfReuse of the pass (needs want_points).  The finish kernel writes its row_map; and when
+        exactly one round is enqueued (speculate == 1) or the rounds are decided one by one (speculate == 0), the SDF
+        evaluation of the first round saves the hidden activations of the dense-set columns for the SDF node.  With
+        more rounds enqueued the final columns come from a merged set: nothing is saved, nothing is paid for."""
         dev = ray_dirs.device
         ray_dirs, cam_loc = _need_gpu(ray_dirs), _need_gpu(cam_loc)
         self._resolve()               # bookkeeping of the previous call (its flags arrived long ago)
@@ -256,10 +283,19 @@ class ErrorBoundSampler(RaySampler):
         a.jitter = jitter.data_ptr() if jitter is not None else None
         a.u_final = u_final.data_ptr() if u_final is not None else None
         a.final_z = final_z.data_ptr()
+        extra_idx = col_slot = None
+        if sdf_reuse is not None:
+            assert want_points and (sdf_reuse.N, sdf_reuse.S, sdf_reuse.n_extra) == (N, S, n_extra)
+            assert sdf_reuse.P == N * S + (4 * N if training else 0)
+            sdf_reuse.flags = flags
+            sdf_reuse.round_pts = pts      # the points of the last round that ran (the first: what the saved rows hold)
+            a.row_map, a.h_saved = sdf_reuse.row_map.data_ptr(), sdf_reuse.h_saved.data_ptr()
+            if sdf_reuse.n_reuse > 0 and speculate in (0, 1):
+                extra_idx, col_slot = self._extra_columns(training, noise, dev, want_slots=True)
         st = _lib.stream_ptr()
         a.M = n_eval
         _lib.call('msdf_sampler_init', C.byref(a), st)
-        z_out = z_eik = x_all = extra_idx = eik_idx = None
+        z_out = z_eik = x_all = eik_idx = None
 
         def prepare_finish():
             """Everything the finish kernel needs -- none of it depends on the number of rounds -- issued while the
@@ -293,7 +329,8 @@ class ErrorBoundSampler(RaySampler):
                     nei = nei_drawn.view(2 * N, 3) if nei is None else nei.to(**f32).contiguous()
                     a.eik_uniform, a.nei_rand = eik_uniform.data_ptr(), nei.data_ptr()
                     self._keep = (eik_uniform, nei)
-            extra_idx = self._extra_columns(training, noise, dev)
+            if extra_idx is None:
+                extra_idx = self._extra_columns(training, noise, dev)[0]
             a.extra_idx = extra_idx.data_ptr()
 
         group = self.global_rounds
@@ -309,7 +346,8 @@ class ErrorBoundSampler(RaySampler):
                 # fused forward kernel on the new points, [N*n_eval, 1]; in a speculated round it returns at once
                 # when the previous round did not ask for this one
                 run_flag = flags.data_ptr() + 4 * (2 * rounds - 1) if (speculate > 0 and rounds > 0) else None
-                new_sdf = net._sdf_only(pts, run_flag=run_flag)
+                save_for = (sdf_reuse, col_slot, n_eval) if (rounds == 0 and col_slot is not None) else None
+                new_sdf = net._sdf_only(pts, run_flag=run_flag, save_for=save_for)
                 a.new_sdf = new_sdf.data_ptr()
                 a.M, a.round_idx = n_eval * (rounds + 1), rounds
                 _lib.call('msdf_sampler_beta', C.byref(a), st)

@@ -276,6 +276,58 @@ def fused_weight_norm(state, layers):
 # ---------------------------------------------------------------------------
 # SDF network
 # ---------------------------------------------------------------------------
+# MSDF_REUSE_SAMPLER_H=0: the forward + gradient kernel computes the hidden layers of every point itself instead of
+# reading those of the dense-set columns from the sampler's first round (SdfReuse); the evaluation order stays permuted.
+# Bit-identical either way (tests/test_gpu_sdf_reuse.py): for comparisons and bisecting.
+REUSE_SAMPLER_H = _os.environ.get('MSDF_REUSE_SAMPLER_H', '1') != '0'
+
+
+class SdfReuse:
+    """What one training / rendering pass shares between the sampler and the SDF node (fp32 core).
+
+    The node's launch grid takes its P = N S (+ eikonal) points in another order than x_all holds them: the n_extra
+    dense-set columns of every ray first (grid row ray * n_extra + e), then the other samples, then the eikonal points.
+    `row_map` (written by msdf_sampler_finish) names the x_all row of every grid row; tensors and workspace keep the
+    x_all order, so every result -- the weight gradients' summation order included -- is what it is without the map.
+    When the sampler stops after one round, the first n_extra N grid rows are points its first round already pushed
+    through the hidden layers: msdf_sdf_forward_save stages those activations in `stage` (grid order) and
+    msdf_sdf_fwd_grad skips the hidden layers of the whole workgroups among them (n_reuse), moving the staged rows to
+    the points' rows of H on the way.  Whether that happens is decided on the device from `flags` and `h_saved`."""
+
+    def __init__(self, mlp, N, S, n_extra, n_eik, save, device):
+        self.mlp, self.N, self.S, self.n_extra, self.save = mlp, N, S, n_extra, bool(save)
+        self.P = N * S + n_eik
+        self.P_pad = _pad64(max(self.P, 1))
+        woff, total = planlib.sdf_workspace(mlp.mp, self.P_pad)
+        if not save:
+            total = woff['PM']
+        self.ws = torch.empty(max(total, 64), device=device, dtype=torch.float32)
+        # staging rows of the saved activations: evaluation order, one H layer block of stage_pad rows per hidden layer
+        self.stage_pad = _pad64(max(N * n_extra, 1))
+        self.stage = torch.empty(mlp.plan.hsum * self.stage_pad, device=device, dtype=torch.float32) \
+            if REUSE_SAMPLER_H else None
+        self.row_map = torch.empty(max(self.P, 1), device=device, dtype=torch.int32)
+        self.h_saved = torch.empty(1, device=device, dtype=torch.int32)       # zeroed by msdf_sampler_init
+        self.flags = None                # the sampler's round flags (set by the sampler)
+        self.round_pts = None            # the sampler's point buffer [N n_eval, 3] (set by the sampler; for tests)
+        self.n_split = N * S
+        # whole workgroups of reused rows; the rows behind them are computed (again) by the node
+        self.n_reuse = (N * n_extra) // 64 * 64 if REUSE_SAMPLER_H else 0
+
+
+def sdf_forward_save(mlp, wpack, bpack, x, clamp_radius, sphere_scale, run_flag, reuse, col_slot, n_cols):
+    """sdf_forward_nograd for the sampler's first round (x: [N n_cols, 3], point ray * n_cols + c) that also saves the
+    hidden activations of the dense-set columns (col_slot[c] >= 0) into reuse.stage."""
+    x = _need_cuda(x, 'points')
+    P = x.shape[0]
+    out = torch.empty(P, 1, device=x.device, dtype=torch.float32)
+    _lib.call('msdf_sdf_forward_save', C.byref(mlp.plan), _lib.ptr(wpack), _lib.ptr(bpack), _lib.ptr(x), None, 0, 0, P,
+              float(clamp_radius), float(sphere_scale), _lib.ptr(out), C.c_void_p(run_flag) if run_flag else None,
+              _lib.ptr(reuse.stage), reuse.stage_pad, _lib.ptr(col_slot), int(n_cols), reuse.n_extra,
+              _lib.ptr(reuse.h_saved), _lib.stream_ptr())
+    return out
+
+
 def sdf_forward_nograd(mlp, wpack, bpack, x, aux, clamp_radius, sphere_scale, run_flag=None, aux_lm=None):
     """get_sdf_vals: forward only (sampler).  run_flag: device address of a uint32; the launch does nothing when
     it holds 0 (a sampler round that the previous round did not ask for).  aux_lm = (C, L C): `aux` is the hash
@@ -297,7 +349,7 @@ _SdfState = collections.namedtuple(
 
 
 def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphere_scale, save, n_split=None,
-                  aux_lm=None, aux_jac=None):
+                  aux_lm=None, aux_jac=None, reuse=None):
     """The msdf_sdf_fwd_grad launch of both SDF nodes.  Returns (outputs, tensors to save, _SdfState); outputs =
     (sdf [:n_split], sdf [n_split:], feat, d sdf/dx [:n_split], d sdf/dx [n_split:], d sdf/d aux or None), the pairs
     being the two halves of one buffer.
@@ -305,7 +357,8 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     tensors [L, P, C] instead of rows [P, 16 * aux_tiles].
     aux_jac = (dy_dx, k) (with aux_lm, C = 2): the encoder's Jacobian [L, P, 3, 2] and the chain-rule factor of
     x -> x01; the kernel then adds the grid part of d sdf / d x to the returned gradient itself, and the backward
-    kernel forms the gradient arriving at d sdf / d aux from it (_sdf_backward's dy_dx and gg_out)."""
+    kernel forms the gradient arriving at d sdf / d aux from it (_sdf_backward's dy_dx and gg_out).
+    reuse: an SdfReuse made for exactly this launch -- its workspace, evaluation order and reusable rows."""
     mp = mlp.mp
     plan = mlp.plan
     x = _need_cuda(x.detach(), 'points')
@@ -317,7 +370,17 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     woff, total = planlib.sdf_workspace(mp, P_pad)
     if not save:
         total = woff['PM']           # only H is touched in inference
-    ws = torch.empty(max(total, 64), device=dev, dtype=torch.float32)
+    if reuse is not None:
+        ns = P if n_split is None else int(n_split)
+        # the eikonal rows are last in both orders and hold every point without features or clamp: the kernel's
+        # workgroup-uniform feature test and its per-point tests mean the same in evaluation order
+        if not (mlp.precision == 'fp32' and reuse.mlp is mlp and reuse.P == P and reuse.P_pad == P_pad and
+                bool(save) == reuse.save and not has_aux and n_feat == n_clamp == ns == reuse.n_split and
+                reuse.n_reuse <= n_feat and reuse.flags is not None):
+            raise RuntimeError('monosdf_amd: SdfReuse does not describe this SDF evaluation')
+        ws = reuse.ws
+    else:
+        ws = torch.empty(max(total, 64), device=dev, dtype=torch.float32)
     F = 16 * plan.feat_tiles
     sdf = torch.empty(P, 1, device=dev, dtype=torch.float32)
     # rows up to the next multiple of 64 exist (zero) so the colour network's weight-gradient GEMM
@@ -346,11 +409,17 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     if aux_jac is not None and aC == 2:
         jac_scale = float(aux_jac[1])
         a.dy_dx, a.aux_dx_scale = aux_jac[0].data_ptr(), jac_scale
+    saved = (x, ws, clamped, wpack, bpack)
+    if reuse is not None:
+        a.row_map, a.n_reuse = reuse.row_map.data_ptr(), reuse.n_reuse
+        a.smp_flags, a.h_saved = reuse.flags.data_ptr(), reuse.h_saved.data_ptr()
+        a.h_stage, a.stage_pad = _addr(reuse.stage), reuse.stage_pad
+        saved += (reuse.row_map,)
     if P > 0:
         _lib.call('msdf_sdf_fwd_grad', C.byref(plan), C.byref(a), _lib.stream_ptr())
     ns = P if n_split is None else int(n_split)
     state = _SdfState(mlp, P, P_pad, n_feat, ns, save, has_aux, (int(aC), int(aLC)), aux_shape, jac_scale)
-    return (sdf[:ns], sdf[ns:], feat, nrm[:ns], nrm[ns:], r_aux), (x, ws, clamped, wpack, bpack), state
+    return (sdf[:ns], sdf[ns:], feat, nrm[:ns], nrm[ns:], r_aux), saved, state
 
 
 def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=None):
@@ -361,7 +430,7 @@ def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=Non
     after_sweeps(g_aux): launches that consume d loss / d aux and should precede the weight-gradient kernels."""
     if not state.saved:
         raise RuntimeError('monosdf_amd: backward through an inference-mode SDF evaluation')
-    x, ws, clamped, wpack, bpack = saved
+    x, ws, clamped, wpack, bpack, *row_map = saved        # row_map: the evaluation order of an SdfReuse launch
     mlp, P, P_pad = state.mlp, state.P, state.P_pad
     mp = mlp.mp
     dev = x.device
@@ -378,6 +447,7 @@ def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=Non
     b.g_feat = _addr(g_feat) if state.n_feat > 0 else None
     b.g_raux = _addr(g_raux) if state.has_aux else None
     b.clamped = clamped.data_ptr()
+    b.row_map = row_map[0].data_ptr() if row_map else None
     base = ws.data_ptr()
     for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST'):
         setattr(b, k, base + 4 * woff[k])
@@ -399,10 +469,10 @@ class SdfMlpFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, aux, flat_w, flat_b, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius,
-                sphere_scale, save, n_split=None):
+                sphere_scale, save, n_split=None, reuse=None):
         ctx.set_materialize_grads(False)
         outs, saved, ctx.state = _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius,
-                                               sphere_scale, save, n_split)
+                                               sphere_scale, save, n_split, reuse=reuse)
         ctx.save_for_backward(*saved)
         return outs
 
@@ -411,7 +481,7 @@ class SdfMlpFunction(torch.autograd.Function):
     def backward(ctx, *grads):
         g_aux, grad = _sdf_backward(ctx.state, ctx.saved_tensors, grads)
         n_w = ctx.state.mlp.mp.n_w
-        return (None, g_aux, grad[:n_w], grad[n_w:]) + (None,) * 9
+        return (None, g_aux, grad[:n_w], grad[n_w:]) + (None,) * 10
 
 
 def _encode_points(x, divide_factor, embeddings, offsets, enc, pitch, level_major, jacobian):
