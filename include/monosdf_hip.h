@@ -254,6 +254,12 @@ typedef struct {
   int32_t n_reuse;
   int32_t stage_pad;
   const float* h_stage;
+  /* Dispatch rotation (fp32 core only; MSDF_ERR_UNSUPPORTED if non-zero on a bf16 core): block b of the launch
+   * evaluates workgroup (b + wg_first) mod n_wg, n_wg = P_pad / 64, so that workgroup wg_first is the first the
+   * hardware starts and wg_first - 1 the last.  With n_reuse > 0, wg_first = n_reuse / 64 starts the workgroups that
+   * compute everything before the shorter reusing ones.  0 <= wg_first < n_wg.  Changes the order in which workgroups
+   * start and nothing else: every workgroup evaluates, reads and writes the rows it does with 0. */
+  int32_t wg_first;
 } msdf_fg_args_t;
 int msdf_sdf_fwd_grad(const msdf_plan_t* plan, const msdf_fg_args_t* args, void* stream);
 

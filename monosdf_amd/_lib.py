@@ -56,7 +56,8 @@ class FgArgs(C.Structure):
                 ('sdf', _P), ('feat', _P), ('nrm', _P), ('r_aux', _P), ('clamped', _P),
                 ('H', _P), ('PM', _P), ('IN0', _P), ('save', C.c_int32), ('aux_C', C.c_int32), ('aux_LC', C.c_int32),
                 ('aux_dx_scale', C.c_float), ('dy_dx', _P),
-                ('row_map', _P), ('smp_flags', _P), ('h_saved', _P), ('n_reuse', C.c_int32), ('stage_pad', C.c_int32), ('h_stage', _P)]
+                ('row_map', _P), ('smp_flags', _P), ('h_saved', _P), ('n_reuse', C.c_int32), ('stage_pad', C.c_int32), ('h_stage', _P),
+                ('wg_first', C.c_int32)]
 
 
 class BwArgs(C.Structure):

@@ -15,11 +15,29 @@ struct PointCtx {
   float x0, x1, x2;
 };
 
+// The workgroup of the launch grid that this block evaluates: the one definition of "which workgroup am I" on the SDF
+// kernels' path.  The hardware starts blocks in index order; wg_first (msdf_fg_args_t.wg_first: the forward + gradient
+// kernel of a core with a row map) rotates the grid so that block b evaluates workgroup (b + wg_first) mod gridDim.x,
+// i.e. workgroup wg_first starts first and wg_first - 1 last.  Which rows a workgroup evaluates does not change.
+// 0 <= wg_first < gridDim.x (the entry point checks it): one conditional subtraction, scalar; the other kernels pass
+// the constant 0 and keep the plain block index.
+template <class Core>
+__device__ __forceinline__ int eval_wg(const int wg_first = 0) {
+  int w = (int)blockIdx.x;
+  if constexpr (Core::ROW_MAP) {
+    if (wg_first > 0) {
+      w += wg_first;
+      if (w >= (int)gridDim.x) w -= (int)gridDim.x;
+    }
+  }
+  return w;
+}
+
 // The row of the workgroup's grid this lane's point sits at: the EVALUATION row.  Without a row map it is also the row
 // of the point in every tensor.
 template <class Core>
-__device__ __forceinline__ int eval_row() {
-  return blockIdx.x * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane_id() & 15);
+__device__ __forceinline__ int eval_row(const int wg) {
+  return wg * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane_id() & 15);
 }
 
 // row_map (cores with ROW_MAP): the point evaluated at row r of the grid is row row_map[r] of the caller's tensors AND
@@ -28,10 +46,11 @@ __device__ __forceinline__ int eval_row() {
 // entry outside [0, P) (a map nobody filled) falls back to the row itself: never an address outside the tensors.
 template <class Core>
 __device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, const int P,
-                                               const int32_t* __restrict__ row_map = nullptr) {
+                                               const int32_t* __restrict__ row_map = nullptr,
+                                               const int wg = eval_wg<Core>()) {
   PointCtx c;
   const int lane = lane_id();
-  const int pe = eval_row<Core>();
+  const int pe = eval_row<Core>(wg);
   c.valid = pe < P;
   c.ptc = c.valid ? pe : (P - 1);
   if constexpr (Core::ROW_MAP) {
@@ -443,7 +462,7 @@ typedef msdf_fg_args_t FgArgs;
 template <class Core>
 __device__ __forceinline__ bool sdf_fwd_grad_reuses(const msdf_plan_t& plan, const FgArgs& a) {
   if constexpr (Core::ROW_MAP) {
-    if ((int)((blockIdx.x + 1) * Core::PTS_PER_WG) <= a.n_reuse && plan.n_layers >= 2 && a.smp_flags != nullptr &&
+    if ((eval_wg<Core>(a.wg_first) + 1) * Core::PTS_PER_WG <= a.n_reuse && plan.n_layers >= 2 && a.smp_flags != nullptr &&
         a.h_saved != nullptr && a.h_stage != nullptr)
       return a.smp_flags[1] == 0u && a.h_saved[0] != 0u;
   }
@@ -455,7 +474,8 @@ __device__ __forceinline__ bool sdf_fwd_grad_reuses(const msdf_plan_t& plan, con
 template <class Core, bool REUSE = false>
 __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const FgArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  const PointCtx c = load_point<Core>(a.x, a.P, a.row_map);
+  const int wg = eval_wg<Core>(a.wg_first);
+  const PointCtx c = load_point<Core>(a.x, a.P, a.row_map, wg);
   const AuxView av = {a.aux_C, a.aux_LC, a.P};
   v4f in[MT], acc[MT];
   const int nl = plan.n_layers;
@@ -472,11 +492,11 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     }
   }
   // workgroup-uniform on purpose: the gemm below contains barriers and cooperative weight staging
-  const bool want_feat = (int)(blockIdx.x * Core::PTS_PER_WG) < a.n_feat;
+  const bool want_feat = wg * Core::PTS_PER_WG < a.n_feat;
 
   // the point's staged row of layer L (REUSE): evaluation order, stage_pad rows per layer block
   auto srow = [&](const msdf_layer_t& L) {
-    return (size_t)L.hpre * (size_t)a.stage_pad + (size_t)eval_row<Core>() * (16 * L.ot) + 4 * c.q;
+    return (size_t)L.hpre * (size_t)a.stage_pad + (size_t)eval_row<Core>(wg) * (16 * L.ot) + 4 * c.q;
   };
   // ---------------- forward chain ----------------
   if constexpr (REUSE) {

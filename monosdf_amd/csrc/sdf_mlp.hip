@@ -188,9 +188,12 @@ extern "C" int msdf_sdf_fwd_grad(const msdf_plan_t* plan, const msdf_fg_args_t* 
   if (a->n_reuse > 0 && (a->row_map == nullptr || a->n_reuse > a->n_feat || a->h_stage == nullptr ||
                          a->stage_pad < a->n_reuse))
     return MSDF_ERR_ARG;
+  // the dispatch rotation names a workgroup of this launch (eval_wg's single conditional subtraction relies on it)
+  if (a->wg_first < 0 || a->wg_first >= a->P_pad / CoreF32::PTS_PER_WG) return MSDF_ERR_ARG;
   return mlp_with_core(plan, [&](auto core) {
     typedef decltype(core) Core;
     if (!Core::AUX_LEVEL_MAJOR && (a->aux_C != 0 || a->dy_dx != nullptr)) return MSDF_ERR_UNSUPPORTED;
+    if (!Core::ROW_MAP && a->wg_first != 0) return MSDF_ERR_UNSUPPORTED;
     return mlp_launch<Core>(fwd_grad_kernel(core), a->P_pad / Core::PTS_PER_WG, stream, *plan, *a);
   });
 }

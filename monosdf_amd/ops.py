@@ -280,6 +280,15 @@ def fused_weight_norm(state, layers):
 # reading those of the dense-set columns from the sampler's first round (SdfReuse); the evaluation order stays permuted.
 # Bit-identical either way (tests/test_gpu_sdf_reuse.py): for comparisons and bisecting.
 REUSE_SAMPLER_H = _os.environ.get('MSDF_REUSE_SAMPLER_H', '1') != '0'
+# MSDF_FG_REUSE_LAST=0: the forward + gradient launch of an SdfReuse starts its workgroups in grid order, the reusing
+# (shorter) ones first, instead of rotated so that they start last (msdf_fg_args_t.wg_first).  Bit-identical
+# either way (tests/test_gpu_fg_dispatch_order.py): for comparisons.
+FG_REUSE_LAST = _os.environ.get('MSDF_FG_REUSE_LAST', '1') != '0'
+
+
+def _fg_wg_first(reuse):
+    """The dispatch rotation of an SdfReuse launch: the first workgroup behind the reusing ones starts first."""
+    return reuse.n_reuse // 64 % (reuse.P_pad // 64) if FG_REUSE_LAST else 0
 
 
 class SdfReuse:
@@ -414,6 +423,7 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
         a.row_map, a.n_reuse = reuse.row_map.data_ptr(), reuse.n_reuse
         a.smp_flags, a.h_saved = reuse.flags.data_ptr(), reuse.h_saved.data_ptr()
         a.h_stage, a.stage_pad = _addr(reuse.stage), reuse.stage_pad
+        a.wg_first = _fg_wg_first(reuse)
         saved += (reuse.row_map,)
     if P > 0:
         _lib.call('msdf_sdf_fwd_grad', C.byref(plan), C.byref(a), _lib.stream_ptr())
