@@ -606,6 +606,55 @@ int msdf_tsdf_face_keep(const float* verts, int64_t n_verts, const int32_t* face
 int msdf_cull_vertices(const float* verts, int64_t n_verts, const float* w2c, int n_views, float fx, float fy, float cx,
                        float cy, int height, int width, uint8_t* seen, void* stream);
 
+/* ---- the DTU evaluation protocol (csrc/dtueval.hip; reference: dtu_eval/evaluate_single_scene.py:20-103 and
+ * dtu_eval/eval.py:43-134).  Integer, boolean, separately rounded fp32 or fp64 rules only and no floating-point
+ * atomics: outputs are bitwise identical run to run.  All buffers are the caller's, on the DEVICE unless said.
+ * msdf_dtu_dilate: out [n_views, height, width] uint8 (0 / 1) = the views of masks (uint8, set iff non-zero) dilated by
+ * skimage's disk(radius), the offsets with dx^2 + dy^2 <= radius^2; pixels outside the image are unset.
+ * 0 <= radius <= 32, n_views * height * width <= 2^37.  workspace: msdf_dtu_dilate_workspace_bytes() bytes (-1 for
+ * sizes out of range), 4-byte aligned, scratch.
+ * msdf_dtu_mask_vertices: keep[i] (uint8) = 1 iff in every view v, with P = proj[v] ([n_views, 12] fp32, rows of the
+ * 3x4 projection whose third row gives camera depth) and separately rounded fp32 operations:
+ * (u, v, z) = ((P0 x + P1 y) + P2 z) + P3 per row, px = u / (z + 1e-6), py = v / (z + 1e-6), the vertex is not valid
+ * (valid: 0 < px < width - 1 and 0 < py < height - 1) or dilated[v, rint(py), rint(px)] != 0 (half to even).  There is
+ * no test of the sign of z.  n_views = 0 keeps every vertex.
+ * msdf_dtu_lattice_count / _emit: the deterministic triangle sampler of eval.py:54-71 in fp64 on the fp32 vertices
+ * (verts [n_verts, 3], faces [n_faces, 3] int32; a face with an index outside [0, n_verts) gives nothing):
+ * v1 = p1 - p0, v2 = p2 - p0, l = sqrt((x^2 + y^2) + z^2), area2 = |v1 x v2| (a face with area2 == 0 gives nothing),
+ * thr = density sqrt(l1 l2 / area2), n = floor(l / thr), candidates a = (i + 0.5) / max(n1, 1e-7), i = 0..n1 and
+ * b = (j + 0.5) / max(n2, 1e-7), j = 0..n2, kept iff a + b < 1, point = (v1 a + v2 b) + p0 rounded once to fp32.
+ * count writes counts[f] (int64; 2^40 for a face of more than 2^34 candidates, which alone exceeds the limit); emit
+ * takes offsets [n_faces + 1] (int64), the exclusive scan of the counts with the total n_points (< 2^31) last, and
+ * writes out [n_points, 3] in the order face, i, j.  density > 0.
+ * msdf_dtu_thin_*: the greedy radius thinning of eval.py:86-94: visiting the points in order, a point still marked is
+ * kept and unmarks every point with ((dx dx + dy dy) + dz dz) <= radius radius (fp64 on the fp32 coordinates).
+ *   _keys: keys[i] (int64) = (cx << 42) | (cy << 21) | cz with c = floor((p - lo) / cell) + 1 per axis in fp64,
+ *     clamped to [1, 2^21 - 2]; the caller chooses lo <= every coordinate and cell >= radius (1 + 2^-10) with
+ *     (max - lo) / cell < 2^21 - 3, so that two points within radius are at most one cell apart.
+ *   _prepare: with perm [n] (int64) the permutation of a sort of the keys, sorted_keys [n] the keys in that order and
+ *     rank [n] (int64; rank[i] = when point i is visited; NULL = index order): fills the workspace
+ *     (msdf_dtu_thin_workspace_bytes(n) bytes, 16-byte aligned) and marks every point undecided.
+ *   _round: one round of the iteration (an undecided point with a kept earlier neighbour becomes removed, else with an
+ *     undecided one stays, else becomes kept); *undecided (uint32) = how many points remain undecided.  The caller
+ *     repeats it until that is 0; the earliest undecided point is decided every round.
+ *   _finish: keep[perm[s]] (uint8) = 1 iff the point is kept. */
+int64_t msdf_dtu_dilate_workspace_bytes(int n_views, int height, int width);
+int msdf_dtu_dilate(const uint8_t* masks, int n_views, int height, int width, int radius, void* workspace,
+                    uint8_t* out, void* stream);
+int msdf_dtu_mask_vertices(const float* verts, int64_t n_verts, const float* proj, int n_views,
+                           const uint8_t* dilated, int height, int width, uint8_t* keep, void* stream);
+int msdf_dtu_lattice_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                           double density, int64_t* counts, void* stream);
+int msdf_dtu_lattice_emit(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, double density,
+                          const int64_t* offsets, int64_t n_points, float* out, void* stream);
+int64_t msdf_dtu_thin_workspace_bytes(int64_t n);
+int msdf_dtu_thin_keys(const float* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell,
+                       int64_t* keys, void* stream);
+int msdf_dtu_thin_prepare(const float* points, const int64_t* perm, const int64_t* rank, const int64_t* sorted_keys,
+                          int64_t n, void* workspace, void* stream);
+int msdf_dtu_thin_round(void* workspace, int64_t n, double radius, uint32_t* undecided, void* stream);
+int msdf_dtu_thin_finish(const void* workspace, const int64_t* perm, int64_t n, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

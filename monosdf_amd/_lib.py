@@ -208,6 +208,16 @@ _SIGNATURES = {
     'msdf_tsdf_face_keep': [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P],
     'msdf_cull_vertices': [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                            _P, _P],
+    'msdf_dtu_dilate_workspace_bytes': [C.c_int, C.c_int, C.c_int],
+    'msdf_dtu_dilate': [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P],
+    'msdf_dtu_mask_vertices': [_P, C.c_int64, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P],
+    'msdf_dtu_lattice_count': [_P, C.c_int64, _P, C.c_int64, C.c_double, _P, _P],
+    'msdf_dtu_lattice_emit': [_P, C.c_int64, _P, C.c_int64, C.c_double, _P, C.c_int64, _P, _P],
+    'msdf_dtu_thin_workspace_bytes': [C.c_int64],
+    'msdf_dtu_thin_keys': [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P],
+    'msdf_dtu_thin_prepare': [_P, _P, _P, _P, C.c_int64, _P, _P],
+    'msdf_dtu_thin_round': [_P, C.c_int64, C.c_double, _P, _P],
+    'msdf_dtu_thin_finish': [_P, _P, C.c_int64, _P, _P],
 }
 
 ABI_VERSION = 8

@@ -10,10 +10,10 @@
 * ``read_ply``: ASCII / binary little-endian PLY meshes written by other programs.
 
 Everything runs on CUDA tensors; there is no CPU path.  Out of scope: ICP alignment (``get_align_transformation``),
-the oriented-bounding-box crop of ``calc_3d_metric`` (eval_recon.py:121-136), the DTU protocol and its mask culling
-(they need the ObsMask files and the mask images), and any grid- or tree-accelerated search: brute force is the exact
-baseline a later one is checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to
-the predicted mesh before it calls these metrics, are in utils/mesh_refuse.py.
+the oriented-bounding-box crop of ``calc_3d_metric`` (eval_recon.py:121-136), and any grid- or tree-accelerated search:
+brute force is the exact baseline a later one is checked against.  View culling and TSDF re-fusion (``refuse``), which
+the reference applies to the predicted mesh before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol
+and its mask culling are in utils/mesh_dtu.py.
 """
 import numpy as np
 import torch

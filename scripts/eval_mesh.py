@@ -1,9 +1,14 @@
 """Metrics of a reconstructed mesh against a ground-truth mesh, on the GPU, as one JSON line.
 
     python scripts/eval_mesh.py PRED.ply GT.ply --protocol scannet|replica [--scale-mat cameras.npz]
+    python scripts/eval_mesh.py PRED.ply --protocol dtu --dtu-dir DTU --scan 24 [--cameras cameras.npz --masks DIR|NPY]
 
 scannet: evaluate() of scannet_eval/evaluate.py (vertex clouds, 2 cm voxel down-sample, 5 cm threshold).
 replica: the metrics of calc_3d_metric() of replica_eval/eval_recon.py (200,000 surface samples per mesh, 5 cm).
+dtu: evaluate_single_scene.py + eval.py of dtu_eval (monosdf_amd/utils/mesh_dtu.py): with --cameras and --masks the mesh
+(in the normalised training frame) is first culled to the dilated object masks and taken to the world frame by
+`scale_mat_0`; without them PRED.ply must be culled and in the world frame already.  --dtu-dir holds the official
+ObsMask/ and Points/stl/ folders.  Prints d2s, s2d and their mean in millimetres.
 --scale-mat: a cameras.npz whose `scale_mat_0` takes the predicted mesh from the normalised training frame to the
 world frame (evaluation/eval.py applies it before it writes the mesh; pass it when PRED.ply was written without).
 The meshes must be aligned already: ICP and the bounding-box crop are not done here (monosdf_amd/utils/mesh_eval.py).
@@ -20,11 +25,34 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def evaluate_dtu(ap, args):
+    from monosdf_amd.utils import mesh_dtu, mesh_eval
+    if args.dtu_dir is None or args.scan is None:
+        ap.error('--protocol dtu needs --dtu-dir and --scan')
+    if (args.cameras is None) != (args.masks is None):
+        ap.error('the mask cull needs both --cameras and --masks')
+    pred = mesh_eval.read_ply(args.pred)
+    if args.cameras:
+        masks = mesh_dtu.read_masks(args.masks)
+        pred = mesh_dtu.cull_to_masks(pred, mesh_dtu.dtu_projections(args.cameras, len(masks)), masks)
+        pred.apply_transform(np.load(args.cameras)['scale_mat_0'])
+    elif args.scale_mat:
+        pred.apply_transform(np.load(args.scale_mat)['scale_mat_0'])
+    scene = mesh_dtu.read_dtu_scene(args.dtu_dir, args.scan)
+    return mesh_dtu.evaluate_dtu(pred, scene['stl_points'], scene['obs_mask'], scene['bb'], scene['res'],
+                                 scene['plane'], density=args.density, seed=args.seed)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('pred')
-    ap.add_argument('gt')
-    ap.add_argument('--protocol', choices=('scannet', 'replica'), required=True)
+    ap.add_argument('gt', nargs='?', default=None, help='scannet, replica: the ground-truth mesh')
+    ap.add_argument('--protocol', choices=('scannet', 'replica', 'dtu'), required=True)
+    ap.add_argument('--dtu-dir', default=None, help='dtu: the official evaluation data (ObsMask/, Points/stl/)')
+    ap.add_argument('--scan', type=int, default=None, help='dtu: the scan number')
+    ap.add_argument('--cameras', default=None, help='dtu: the scene\'s cameras.npz, for the mask cull')
+    ap.add_argument('--masks', default=None, help='dtu: the scene\'s mask directory or an .npy stack [n, H, W]')
+    ap.add_argument('--density', type=float, default=0.2, help='dtu: sampling and thinning distance')
     ap.add_argument('--scale-mat', default=None)
     ap.add_argument('--threshold', type=float, default=0.05)
     ap.add_argument('--down-sample', type=float, default=0.02, help='scannet: voxel size (0: none)')
@@ -32,6 +60,11 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args()
     from monosdf_amd.utils import mesh_eval
+    if args.protocol == 'dtu':
+        print(json.dumps(evaluate_dtu(ap, args)))
+        return
+    if args.gt is None:
+        ap.error('--protocol %s needs PRED.ply and GT.ply' % args.protocol)
     pred, gt = mesh_eval.read_ply(args.pred), mesh_eval.read_ply(args.gt)
     if args.scale_mat:
         pred.apply_transform(np.load(args.scale_mat)['scale_mat_0'])
