@@ -1,7 +1,10 @@
 // The embedding-table gradient of the hash grid ("scatter"): its three forms -- one float atomic per corner
 // (hg_scatter_*), binned with exact bin sizes (hb_*), binned with fixed regions (hb2_*: what the training step runs) --
 // and the one host launcher that chooses between them, hg_table_gradient.  Included by hashgrid.hip alone, after the
-// cell and level helpers the kernels use (HgCell, HgLevel, hg_index, hg_locate): one translation unit, its -ffp-contract=off.
+// cell and level helpers the kernels use (HgCell, HgLevel, hg_locate, hg_corner_index, HgCorners): one translation unit,
+// its -ffp-contract=off.  The three forms differ only in how a corner's value reaches the table: which value goes to
+// which entry is hg_corner_value and hg_corner_index for all of them; the binned forms share the record (hb_write_record /
+// hb_read_record), the block scan (hb_block_scan) and the flush of a summed slice (hb_flush_slice).
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -12,34 +15,8 @@
 // instruction as one-point-per-lane, which is what the memory-side atomic units are paced by
 // (MI355X_MICROARCH.md "Global float atomics", access-shape row).
 // ---------------------------------------------------------------------------
-// value added to corner k of (point b, level, channel ch):
-//   SECOND = false: w_k * grad                                         (kernel_grid_backward, cu:257-343)
-//   SECOND = true : (sum over axes of +/- prod of the other axes' weights * gg_x * dsmooth * scale) * grad
-//                                                                      (kernel_grid_second_backward_embedding, cu:431-595)
-template <bool SECOND>
-__device__ __forceinline__ void hg_corner_values(const HgCell& c, const float g, const float* __restrict__ gg_inputs,
-                                                 const uint32_t b, float (&val)[8], uint32_t (&idx)[8]) {
-  const float wx[2] = {1.f - c.sx, c.sx}, wy[2] = {1.f - c.sy, c.sy}, wz[2] = {1.f - c.sz, c.sz};
-  float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-  if (SECOND) {
-    q0 = gg_inputs[(size_t)b * 3 + 0] * c.dx * c.scale;
-    q1 = gg_inputs[(size_t)b * 3 + 1] * c.dy * c.scale;
-    q2 = gg_inputs[(size_t)b * 3 + 2] * c.dz * c.scale;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
-    float w;
-    if (SECOND)
-      w = (bx ? 1.f : -1.f) * wy[by] * wz[bz] * q0 + (by ? 1.f : -1.f) * wx[bx] * wz[bz] * q1 +
-          (bz ? 1.f : -1.f) * wx[bx] * wy[by] * q2;
-    else
-      w = wx[bx] * wy[by] * wz[bz];
-    val[k] = w * g;
-    idx[k] = hg_index(c.gx + bx, c.gy + by, c.gz + bz, c.hsize, c.res);
-  }
-}
-
+// value added to corner k of (point b, level, channel ch): hg_corner_value<SECOND> (MODE 0: kernel_grid_backward,
+// MODE 1: kernel_grid_second_backward_embedding), at entry hg_corner_index.
 // levels [level_base, level_base + gridDim.y): straight to memory
 template <int C, bool SECOND>
 __global__ void __launch_bounds__(HG_THREADS)
@@ -50,13 +27,19 @@ hg_scatter_kernel(const float* __restrict__ grad, const float* __restrict__ inpu
   const uint32_t b = t / C, ch = t % C;
   if (b >= B) return;
   const uint32_t level = level_base + blockIdx.y;
-  const HgCell c = hg_locate(inputs, offsets, b, level, S, H);
+  const HgLevel lv = hg_level(offsets, level, S, H);
+  const HgCell c = hg_locate(inputs, lv, b);
   if (c.oob) return;
   const float g = grad[((size_t)level * B + b) * C + ch];
   float* table = grad_grid + (size_t)(uint32_t)offsets[level] * C + ch;
+  const HgCorners cn(c, SECOND ? gg_inputs + (size_t)b * 3 : nullptr);
   float val[8];
   uint32_t idx[8];
-  hg_corner_values<SECOND>(c, g, gg_inputs, b, val, idx);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    val[k] = hg_corner_value<SECOND ? 1 : 0>(cn.weight(k), cn.coefficient(k), g, 0.f);
+    idx[k] = hg_corner_index(lv, c, k);
+  }
 #pragma unroll
   for (int k = 0; k < 8; ++k) unsafeAtomicAdd(table + (size_t)idx[k] * C, val[k]);
 }
@@ -77,8 +60,8 @@ hg_scatter_lds_kernel(const float* __restrict__ grad, const float* __restrict__ 
                       const uint32_t lds_floats) {
   extern __shared__ float hg_tab[];
   const uint32_t level = blockIdx.y;
-  const uint32_t hsize = (uint32_t)(offsets[level + 1] - offsets[level]);
-  const uint32_t n = hsize * C;
+  const HgLevel lv = hg_level(offsets, level, S, H);
+  const uint32_t n = lv.hsize * C;
   const bool in_lds = n <= lds_floats;       // host-side sizing is an estimate: fall back if the level is larger
   float* table = grad_grid + (size_t)(uint32_t)offsets[level] * C;
   // LDS atomics (~64 lanes per 32 cycles per CU, several same-address lanes per instruction on these levels) are
@@ -91,15 +74,19 @@ hg_scatter_lds_kernel(const float* __restrict__ grad, const float* __restrict__ 
   }
   const uint32_t per = (B + n_wg - 1) / n_wg;
   const uint32_t b_end = min(B, (blockIdx.x + 1) * per);
-  const HgLevel lv = hg_level(offsets, level, S, H);
   for (uint32_t t = blockIdx.x * per * C + threadIdx.x; t < b_end * C; t += HG_LDS_THREADS) {
     const uint32_t b = t / C, ch = t % C;
     const HgCell c = hg_locate(inputs, lv, b);
     if (c.oob) continue;
     const float g = grad[((size_t)level * B + b) * C + ch];
+    const HgCorners cn(c, SECOND ? gg_inputs + (size_t)b * 3 : nullptr);
     float val[8];
     uint32_t idx[8];
-    hg_corner_values<SECOND>(c, g, gg_inputs, b, val, idx);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      val[k] = hg_corner_value<SECOND ? 1 : 0>(cn.weight(k), cn.coefficient(k), g, 0.f);
+      idx[k] = hg_corner_index(lv, c, k);
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (in_lds) atomicAdd(&hg_tab[idx[k] * C + ch], val[k]);
@@ -119,12 +106,11 @@ hg_scatter_lds_kernel(const float* __restrict__ grad, const float* __restrict__ 
   }
 }
 
-// number of leading levels whose dense table fits the LDS budget, from the kernel's own resolution formula
+// number of leading levels whose dense table fits the LDS budget, from the kernels' own resolution formula
 static uint32_t hg_small_levels(const uint32_t C, const uint32_t L, const float S, const uint32_t H, uint32_t* lds_bytes) {
   uint32_t n = 0, bytes = 0;
   for (uint32_t l = 0; l < L; ++l) {
-    const float scale = (float)exp2((double)((float)l * S)) * (float)H - 1.0f;
-    const double res = (double)((uint32_t)ceilf(scale) + 1u);
+    const double res = (double)hg_resolution(l, S, H).res;
     const double b = res * res * res * C * 4.0;
     if (b > (double)HG_LDS_MAX_BYTES) break;
     bytes = (uint32_t)b > bytes ? (uint32_t)b : bytes;
@@ -180,7 +166,40 @@ static int hg_launch_scatter(const float* grad, const float* inputs, const int* 
 #define HB_THREADS 256
 #define HB_PTS 4                      // points per thread in the count / place kernels (1,024 per workgroup)
 #define HB_MAX_SLICES 1024            // per level, in the LDS histogram (2^19 entries x C = 8 -> 512)
+#define HB_RANK_SHIFT 19              // first form: a corner between the place kernel's phases is (index | rank << 19)
 #define HB_HDR_INTS 16
+#define HB_REGION_RECORDS (8 * HB_PTS * HB_THREADS)   // corners of one place workgroup: the second form's fixed region
+
+// A record is {entry in slice, C floats}: 1 + C dwords at position `pos` of a record array.
+__host__ __device__ constexpr uint32_t hb_record_dwords(const uint32_t C) { return 1 + C; }
+template <int C>
+__device__ __forceinline__ void hb_write_record(uint32_t* __restrict__ rec, const size_t pos, const uint32_t entry,
+                                                const float (&v)[C]) {
+  uint32_t* r = rec + pos * hb_record_dwords(C);
+  r[0] = entry;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) r[1 + ch] = __float_as_uint(v[ch]);
+}
+template <int C>
+__device__ __forceinline__ void hb_read_record(const uint32_t* __restrict__ rec, const size_t pos, uint32_t& entry,
+                                               float (&v)[C]) {
+  const uint32_t* r = rec + pos * hb_record_dwords(C);
+  entry = r[0];
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) v[ch] = __uint_as_float(r[1 + ch]);
+}
+
+// Inclusive scan of a[0 .. N) in LDS, in place, by the N threads of a workgroup (t = its thread index; Hillis-Steele).
+// A barrier stands between the caller's writes of a[] and the call; the result is visible to all threads on return.
+template <int N>
+__device__ __forceinline__ void hb_block_scan(int* a, const int t) {
+  for (int d = 1; d < N; d <<= 1) {
+    const int x = (t >= d) ? a[t - d] : 0;
+    __syncthreads();
+    a[t] += x;
+    __syncthreads();
+  }
+}
 
 struct HbLayout {                      // int32 offsets into the workspace
   int nb_max, work_max, slice_base, bin_count, bin_base, bin_cursor, work, hdr_ints;
@@ -197,7 +216,7 @@ static HbLayout hb_layout(const uint32_t B, const uint32_t C, const uint32_t L, 
   y.work = (y.bin_cursor + y.nb_max + 3) & ~3;          // int4 descriptors, 16-byte aligned
   y.hdr_ints = y.work + 4 * y.work_max;
   y.rec_off_bytes = (((size_t)y.hdr_ints * 4) + 255) & ~(size_t)255;
-  y.total_bytes = y.rec_off_bytes + (size_t)B * L * 8 * (4 + 4 * C);
+  y.total_bytes = y.rec_off_bytes + (size_t)B * L * 8 * 4 * hb_record_dwords(C);
   return y;
 }
 
@@ -240,7 +259,7 @@ hb_count_k(const float* __restrict__ inputs, const int* __restrict__ offsets, in
     if (c.oob) continue;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const uint32_t idx = hg_index(c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1), c.hsize, c.res);
+      const uint32_t idx = hg_corner_index(lv, c, k);
       const int s = (int)(idx / epb);
       if (local) atomicAdd(&hist[s], 1);
       else atomicAdd(&ws[y.bin_count + sb + s], 1);
@@ -273,12 +292,8 @@ hb_scan_k(int* __restrict__ ws, const HbLayout y, const int* __restrict__ offset
   }
   part[t] = s; partw[t] = w;
   __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {            // Hillis-Steele inclusive scan of the per-thread totals
-    const int a = (t >= d) ? part[t - d] : 0, aw = (t >= d) ? partw[t - d] : 0;
-    __syncthreads();
-    part[t] += a; partw[t] += aw;
-    __syncthreads();
-  }
+  hb_block_scan<1024>(part, t);                   // the per-thread totals
+  hb_block_scan<1024>(partw, t);
   int run = part[t] - s, runw = partw[t] - w;
   const uint32_t epb = HB_SLICE_FLOATS / C;
   int level = 0;
@@ -291,14 +306,15 @@ hb_scan_k(int* __restrict__ ws, const HbLayout y, const int* __restrict__ offset
     const uint32_t hsize = (uint32_t)(offsets[level + 1] - offsets[level]);
     const int nf = (int)(min(epb, hsize - e0) * C);
     const int chunks = (n + HB_CHUNK - 1) / HB_CHUNK;
+    // hashed as the index function has it, by its 32-bit running stride (the flag only selects the LDS add of
+    // hb_accumulate_k: no result depends on it)
+    const bool hashed = !hg_level(offsets, (uint32_t)level, S, H).dense;
     for (int c = 0; c < chunks; ++c) {
       int* d = ws + y.work + 4 * (runw + c);
       d[0] = run + c * HB_CHUNK;
       d[1] = min(run + n, run + (c + 1) * HB_CHUNK);
       d[2] = (int)(((uint32_t)offsets[level] + e0) * C);   // < 2^31 floats: tables of up to 8 GB
       // bit 30: several workgroups share the slice; bit 29: hashed level (its records rarely repeat an entry)
-      const uint64_t res = (uint64_t)ceilf((float)exp2((double)((float)level * S)) * (float)H - 1.0f) + 1u;
-      const bool hashed = res * res * res > (uint64_t)hsize;
       d[3] = nf | (chunks > 1 ? (int)0x40000000 : 0) | (hashed ? (int)0x20000000 : 0);
     }
     run += n;
@@ -310,11 +326,10 @@ hb_scan_k(int* __restrict__ ws, const HbLayout y, const int* __restrict__ offset
   }
 }
 
-// MODE 0: w_k * grad  (kernel_grid_backward);  MODE 1: second-order coefficient * grad
-// (kernel_grid_second_backward_embedding);  MODE 2: w_k * grad + coefficient * grad2, both in one pass.
+// MODE: which of its terms a record holds, hg_corner_value<MODE>.
 // A workgroup takes 1,024 points of one level: phase 1 ranks every corner inside (workgroup, bin) with an LDS
 // histogram, one returning global atomic per non-empty bin then reserves the workgroup's run in the bin, phase 2
-// writes the records.  (index in level | rank << 19) is all that is kept per corner between the phases.
+// writes the records.  (index in level | rank << HB_RANK_SHIFT) is all that is kept per corner between the phases.
 template <int C, int MODE>
 __global__ void __launch_bounds__(HB_THREADS)
 hb_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, const float* __restrict__ inputs,
@@ -325,27 +340,25 @@ hb_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, cons
   const int sb = ws[y.slice_base + level];
   const int ns = ws[y.slice_base + level + 1] - sb;
   const HgLevel lv = hg_level(offsets, level, S, H);
-  // packed (index | rank << 19) needs index < 2^19 and rank < 2^13 (8 * 1,024 records per workgroup)
-  const bool local = ns <= HB_MAX_SLICES && lv.hsize <= (1u << 19);
+  // packed (index | rank << 19) needs index < 2^19 and rank < 2^13 (HB_REGION_RECORDS = 8 * 1,024 per workgroup)
+  const bool local = ns <= HB_MAX_SLICES && lv.hsize <= (1u << HB_RANK_SHIFT);
   if (local) {
     for (int i = threadIdx.x; i < ns; i += HB_THREADS) hist[i] = 0;
     __syncthreads();
   }
   constexpr uint32_t epb = HB_SLICE_FLOATS / C;
   uint32_t packed[HB_PTS][8];
-  uint32_t live = 0;
 #pragma unroll
   for (int p = 0; p < HB_PTS; ++p) {
     const uint32_t b = (blockIdx.x * HB_PTS + p) * HB_THREADS + threadIdx.x;
     if (b >= B) continue;
     const HgCell c = hg_locate(inputs, lv, b);
     if (c.oob) continue;
-    live |= 1u << p;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const uint32_t idx = hg_index(c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1), c.hsize, c.res);
+      const uint32_t idx = hg_corner_index(lv, c, k);
       const int s = (int)(idx / epb);
-      if (local) packed[p][k] = idx | ((uint32_t)atomicAdd(&hist[s], 1) << 19);
+      if (local) packed[p][k] = idx | ((uint32_t)atomicAdd(&hist[s], 1) << HB_RANK_SHIFT);
       else packed[p][k] = (uint32_t)atomicAdd(&ws[y.bin_cursor + sb + s], 1);     // absolute record position
     }
   }
@@ -360,16 +373,11 @@ hb_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, cons
   uint32_t* rec = (uint32_t*)((char*)ws + y.rec_off_bytes);
 #pragma unroll
   for (int p = 0; p < HB_PTS; ++p) {
-    if (!(live & (1u << p))) continue;
     const uint32_t b = (blockIdx.x * HB_PTS + p) * HB_THREADS + threadIdx.x;
+    if (b >= B) continue;
     const HgCell c = hg_locate(inputs, lv, b);
-    const float wx[2] = {1.f - c.sx, c.sx}, wy[2] = {1.f - c.sy, c.sy}, wz[2] = {1.f - c.sz, c.sz};
-    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-    if (MODE != 0) {
-      q0 = gg_inputs[(size_t)b * 3 + 0] * c.dx * c.scale;
-      q1 = gg_inputs[(size_t)b * 3 + 1] * c.dy * c.scale;
-      q2 = gg_inputs[(size_t)b * 3 + 2] * c.dz * c.scale;
-    }
+    if (c.oob) continue;
+    const HgCorners cn(c, MODE != 0 ? gg_inputs + (size_t)b * 3 : nullptr);
     float g1[C], g2[C];
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
@@ -378,28 +386,19 @@ hb_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, cons
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
-      const float wk = wx[bx] * wy[by] * wz[bz];
-      const float qk = (bx ? 1.f : -1.f) * wy[by] * wz[bz] * q0 + (by ? 1.f : -1.f) * wx[bx] * wz[bz] * q1 +
-                       (bz ? 1.f : -1.f) * wx[bx] * wy[by] * q2;
+      const float wk = cn.weight(k), qk = cn.coefficient(k);
       uint32_t idx, pos;
       if (local) {
-        idx = packed[p][k] & ((1u << 19) - 1);
-        pos = (uint32_t)hist[idx / epb] + (packed[p][k] >> 19);
+        idx = packed[p][k] & ((1u << HB_RANK_SHIFT) - 1);
+        pos = (uint32_t)hist[idx / epb] + (packed[p][k] >> HB_RANK_SHIFT);
       } else {
-        idx = hg_index(c.gx + bx, c.gy + by, c.gz + bz, c.hsize, c.res);
+        idx = hg_corner_index(lv, c, k);
         pos = packed[p][k];
       }
-      uint32_t* r = rec + (size_t)pos * (1 + C);
-      r[0] = idx % epb;
+      float v[C];
 #pragma unroll
-      for (int ch = 0; ch < C; ++ch) {
-        float v;
-        if (MODE == 0) v = wk * g1[ch];
-        else if (MODE == 1) v = qk * g1[ch];
-        else v = wk * g1[ch] + qk * g2[ch];
-        r[1 + ch] = __float_as_uint(v);
-      }
+      for (int ch = 0; ch < C; ++ch) v[ch] = hg_corner_value<MODE>(wk, qk, g1[ch], g2[ch]);
+      hb_write_record<C>(rec, pos, idx % epb, v);
     }
   }
 }
@@ -416,6 +415,48 @@ __device__ __forceinline__ void lds_add_cas(float* p, const float v) {
     const uint32_t got = atomicCAS(u, old, __float_as_uint(sum));
     if (got == old) break;
     old = got;
+  }
+}
+
+// The tail of both accumulate kernels: the slice summed in LDS goes to its `ne` entries of the table.  acc(i, ch) reads
+// channel ch of entry i from the accumulator (the two forms lay it out differently).
+template <int C, typename Acc>
+__device__ __forceinline__ void hb_flush_slice(float* __restrict__ table, const uint32_t ne, const bool shared_slice,
+                                               const bool overwrite, const Acc acc) {
+  const uint32_t tid = threadIdx.x;
+  if (shared_slice) {
+    for (uint32_t i = tid; i < ne * C; i += HB_THREADS) {
+      const float v = acc(i / C, i % C);
+      if (v != 0.f) unsafeAtomicAdd(table + i, v);  // neighbouring lanes, neighbouring floats: the fast atomic shape
+    }
+    return;
+  }
+  // this workgroup owns the slice: plain read-modify-write, one entry (C floats) per lane and step.  Level offsets
+  // are arbitrary entry counts (12,167 ...), so a table row is aligned to one entry, not to 16 bytes.
+  typedef float vcf __attribute__((ext_vector_type(C)));
+  vcf* tc = (vcf*)table;
+  const auto entry = [&](const uint32_t i) {
+    vcf a;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) a[ch] = acc(i, ch);
+    return a;
+  };
+  if (overwrite) {                         // the table gradient is an output, not an accumulator: nothing to read
+    for (uint32_t i = tid; i < ne; i += HB_THREADS) tc[i] = entry(i);
+    return;
+  }
+  constexpr int UF = 8;
+  for (uint32_t i0 = tid; i0 < ne; i0 += UF * HB_THREADS) {
+    vcf t[UF];
+    // all loads issued (index clamped to the last entry): a branch around a load makes the compiler wait for each one
+    // in turn (cdna_hip_programming.md, "Projection GEMM" item 4c)
+#pragma unroll
+    for (int u = 0; u < UF; ++u) t[u] = tc[min(i0 + u * HB_THREADS, ne - 1)];
+#pragma unroll
+    for (int u = 0; u < UF; ++u) {
+      const uint32_t i = i0 + u * HB_THREADS;
+      if (i < ne) tc[i] = t[u] + entry(i);
+    }
   }
 }
 
@@ -442,13 +483,7 @@ hb_accumulate_k(const int* __restrict__ ws, const HbLayout y, float* __restrict_
     // every load is issued (index clamped to the last record): a branch around a load makes the compiler wait for
     // each one in turn (cdna_hip_programming.md, "Projection GEMM" item 4c)
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = min(i0 + u * HB_THREADS, r1 - 1);
-      const uint32_t* r = rec + (size_t)i * (1 + C);
-      e[u] = r[0];
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch) v[u][ch] = __uint_as_float(r[1 + ch]);
-    }
+    for (int u = 0; u < U; ++u) hb_read_record<C>(rec, (size_t)min(i0 + u * HB_THREADS, r1 - 1), e[u], v[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (i0 + u * HB_THREADS < r1) {
@@ -467,35 +502,8 @@ hb_accumulate_k(const int* __restrict__ ws, const HbLayout y, float* __restrict_
     }
   }
   __syncthreads();
-  float* table = grad_grid + (size_t)(uint32_t)d.z;
-  if (!shared_slice) {
-    // this workgroup owns the slice: plain read-modify-write, one entry (C floats) per lane and step.  Level offsets
-    // are arbitrary entry counts (12,167 ...), so a table row is aligned to one entry, not to 16 bytes.
-    typedef float vcf __attribute__((ext_vector_type(C)));
-    vcf* tc = (vcf*)table;
-    const uint32_t ne = nf / C;
-    constexpr int UF = 8;
-    for (uint32_t i0 = threadIdx.x; i0 < ne; i0 += UF * HB_THREADS) {
-      vcf t[UF];
-#pragma unroll
-      for (int u = 0; u < UF; ++u) t[u] = tc[min(i0 + u * HB_THREADS, ne - 1)];      // all loads issued, see above
-#pragma unroll
-      for (int u = 0; u < UF; ++u) {
-        const uint32_t i = i0 + u * HB_THREADS;
-        if (i < ne) {
-          vcf a;
-#pragma unroll
-          for (int ch = 0; ch < C; ++ch) a[ch] = acc[ch * epb + i];
-          tc[i] = t[u] + a;
-        }
-      }
-    }
-  } else {
-    for (uint32_t i = threadIdx.x; i < nf; i += HB_THREADS) {
-      const float v = acc[(i % C) * epb + i / C];
-      if (v != 0.f) unsafeAtomicAdd(table + i, v);  // neighbouring lanes, neighbouring floats: the fast atomic shape
-    }
-  }
+  hb_flush_slice<C>(grad_grid + (size_t)(uint32_t)d.z, nf / C, shared_slice, false,
+                    [&](const uint32_t i, const uint32_t ch) { return acc[ch * epb + i]; });
 }
 
 // ---------------------------------------------------------------------------
@@ -532,7 +540,7 @@ static Hb2Layout hb2_layout(const uint32_t B, const uint32_t C, const uint32_t L
   // items of a level: slices x ceil(n_wg / min(slices, n_wg)) <= slices + n_wg
   y.work_max = (int)((n_entries * C + HB_SLICE_FLOATS - 1) / HB_SLICE_FLOATS + L) + (int)L * y.n_wg;
   y.rec_off_bytes = (((size_t)L * y.n_wg * y.rt_stride * 4) + 255) & ~(size_t)255;
-  y.total_bytes = y.rec_off_bytes + (size_t)L * y.n_wg * (8 * HB_PTS * HB_THREADS) * (4 + 4 * C);
+  y.total_bytes = y.rec_off_bytes + (size_t)L * y.n_wg * HB_REGION_RECORDS * 4 * hb_record_dwords(C);
   return y;
 }
 
@@ -619,10 +627,8 @@ hb2_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, con
     for (int k = 0; k < 8; k += 2) {
       uint32_t r0 = 0, r1 = 0;
       if (head) {
-        const uint32_t i0 = hg_index_lv(lv, c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1));
-        const uint32_t i1 = hg_index_lv(lv, c.gx + ((k + 1) & 1), c.gy + (((k + 1) >> 1) & 1), c.gz + (((k + 1) >> 2) & 1));
-        r0 = (uint32_t)atomicAdd(&hist[i0 / epb], 1);
-        r1 = (uint32_t)atomicAdd(&hist[i1 / epb], 1);
+        r0 = (uint32_t)atomicAdd(&hist[hg_corner_index(lv, c, k) / epb], 1);
+        r1 = (uint32_t)atomicAdd(&hist[hg_corner_index(lv, c, k + 1) / epb], 1);
       }
       rank2[p][k >> 1] = r0 | (r1 << 16);
     }
@@ -637,12 +643,7 @@ hb2_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, con
     for (int i = lo; i < hi; ++i) sum += hist[i];
     part[tid] = sum;
     __syncthreads();
-    for (int d = 1; d < HB_THREADS; d <<= 1) {
-      const int a = (tid >= d) ? part[tid - d] : 0;
-      __syncthreads();
-      part[tid] += a;
-      __syncthreads();
-    }
+    hb_block_scan<HB_THREADS>(part, tid);
     int run = part[tid] - sum;
     int* rt = ws + ((size_t)level * y.n_wg + blockIdx.x) * y.rt_stride;
     for (int i = lo; i < hi; ++i) {
@@ -657,7 +658,7 @@ hb2_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, con
 
   // ---- phase 3: the records ----
   uint32_t* rec = (uint32_t*)((char*)ws + y.rec_off_bytes) +
-                  ((size_t)level * y.n_wg + blockIdx.x) * (8 * HB_PTS * HB_THREADS) * (1 + C);
+                  ((size_t)level * y.n_wg + blockIdx.x) * HB_REGION_RECORDS * hb_record_dwords(C);   // this workgroup's region
 #pragma unroll
   for (int p = 0; p < HB_PTS; ++p) {
     const uint32_t b = (blockIdx.x * HB_PTS + p) * HB_THREADS + tid;
@@ -669,6 +670,8 @@ hb2_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, con
     const float m2 = (live && dpp_u32<DPP_ROW_SHL(2)>(rid[p]) == rid[p]) ? 1.f : 0.f;
     const float m4 = (live && dpp_u32<DPP_ROW_SHL(4)>(rid[p]) == rid[p]) ? 1.f : 0.f;
     const float m8 = (live && dpp_u32<DPP_ROW_SHL(8)>(rid[p]) == rid[p]) ? 1.f : 0.f;
+    // the operands of HgCorners as plain locals: through the struct the compiler packs the products of phase 3
+    // differently and this kernel takes 93 instead of 86 VGPRs at C = 2, MODE 2 (84 instead of 76 at MODE 1, a wave less)
     const float wx[2] = {1.f - c.sx, c.sx}, wy[2] = {1.f - c.sy, c.sy}, wz[2] = {1.f - c.sz, c.sz};
     float q0 = 0.f, q1 = 0.f, q2 = 0.f;
     if (MODE != 0) {
@@ -685,25 +688,15 @@ hb2_place_k(const float* __restrict__ grad, const float* __restrict__ grad2, con
     const bool head = (heads >> p) & 1u;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
-      const float wk = wx[bx] * wy[by] * wz[bz];
-      const float qk = (bx ? 1.f : -1.f) * wy[by] * wz[bz] * q0 + (by ? 1.f : -1.f) * wx[bx] * wz[bz] * q1 +
-                       (bz ? 1.f : -1.f) * wx[bx] * wy[by] * q2;
+      const float wk = hg_corner_weight(wx, wy, wz, k), qk = hg_corner_coefficient(wx, wy, wz, q0, q1, q2, k);
       float v[C];
 #pragma unroll
-      for (int ch = 0; ch < C; ++ch) {
-        if (MODE == 0) v[ch] = wk * g1[ch];
-        else if (MODE == 1) v[ch] = qk * g1[ch];
-        else v[ch] = wk * g1[ch] + qk * g2[ch];
-      }
+      for (int ch = 0; ch < C; ++ch) v[ch] = hg_corner_value<MODE>(wk, qk, g1[ch], g2[ch]);
       run_sum<C>(v, m1, m2, m4, m8);
       if (head) {
-        const uint32_t idx = hg_index_lv(lv, c.gx + bx, c.gy + by, c.gz + bz);
+        const uint32_t idx = hg_corner_index(lv, c, k);
         const uint32_t pos = (uint32_t)hist[idx / epb] + ((rank2[p][k >> 1] >> ((k & 1) * 16)) & 0xffffu);
-        uint32_t* r = rec + (size_t)pos * (1 + C);
-        r[0] = idx % epb;
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) r[1 + ch] = __float_as_uint(v[ch]);
+        hb_write_record<C>(rec, pos, idx % epb, v);
       }
     }
   }
@@ -756,7 +749,6 @@ hb2_accumulate_k(const int* __restrict__ ws, const Hb2Layout y, const int* __res
   const int tid = threadIdx.x;
   for (uint32_t i = tid; i < HB_SLICE_FLOATS / 4; i += HB_THREADS) ((v4f*)acc)[i] = (v4f){0.f, 0.f, 0.f, 0.f};
   const uint32_t* rec_all = (const uint32_t*)((const char*)ws + y.rec_off_bytes);
-  constexpr size_t REGION = (size_t)(8 * HB_PTS * HB_THREADS) * (1 + C);        // dwords per place workgroup
   for (int t0 = wg0; t0 < wg1; t0 += HB2_TILE) {
     // this pass's runs: start and length per place workgroup, inclusive scan of the lengths
     const int wg = t0 + tid;
@@ -771,12 +763,7 @@ hb2_accumulate_k(const int* __restrict__ ws, const Hb2Layout y, const int* __res
     pre[tid + 1] = n;
     if (tid == 0) pre[0] = 0;
     __syncthreads();
-    for (int d = 1; d < HB2_TILE; d <<= 1) {
-      const int a = (tid >= d) ? pre[tid + 1 - d] : 0;
-      __syncthreads();
-      pre[tid + 1] += a;
-      __syncthreads();
-    }
+    hb_block_scan<HB2_TILE>(pre + 1, tid);
     const int total = pre[HB2_TILE];
     constexpr int U = 4;
     for (int i0 = tid; i0 < total; i0 += U * HB_THREADS) {
@@ -789,10 +776,8 @@ hb2_accumulate_k(const int* __restrict__ ws, const Hb2Layout y, const int* __res
 #pragma unroll
         for (int step = HB2_TILE / 2; step > 0; step >>= 1)
           if (pre[j + step] <= i) j += step;
-        const uint32_t* r = rec_all + ((size_t)level * y.n_wg + t0 + j) * REGION + (size_t)(st[j] + i - pre[j]) * (1 + C);
-        e[u] = r[0];
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) v[u][ch] = __uint_as_float(r[1 + ch]);
+        hb_read_record<C>(rec_all, ((size_t)level * y.n_wg + t0 + j) * HB_REGION_RECORDS + (size_t)(st[j] + i - pre[j]),
+                          e[u], v[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -801,36 +786,8 @@ hb2_accumulate_k(const int* __restrict__ ws, const Hb2Layout y, const int* __res
   }
   __syncthreads();
   const uint32_t e0 = (uint32_t)slice * epb;
-  const uint32_t nf = min(epb, hsize - e0) * C;
-  float* table = grad_grid + ((size_t)(uint32_t)offsets[level] + e0) * C;
-  if (!shared_slice) {
-    // this workgroup owns the slice: plain read-modify-write, one entry (C floats) per lane and step.  Level offsets
-    // are arbitrary entry counts (12,167 ...), so a table row is aligned to one entry, not to 16 bytes.
-    typedef float vcf __attribute__((ext_vector_type(C)));
-    vcf* tc = (vcf*)table;
-    const vcf* ac = (const vcf*)acc;
-    const uint32_t ne = nf / C;
-    if (overwrite) {                       // the table gradient is an output, not an accumulator: nothing to read
-      for (uint32_t i = tid; i < ne; i += HB_THREADS) tc[i] = ac[i];
-    } else {
-      constexpr int UF = 8;
-      for (uint32_t i0 = tid; i0 < ne; i0 += UF * HB_THREADS) {
-        vcf t[UF];
-#pragma unroll
-        for (int u = 0; u < UF; ++u) t[u] = tc[min(i0 + u * HB_THREADS, ne - 1)];
-#pragma unroll
-        for (int u = 0; u < UF; ++u) {
-          const uint32_t i = i0 + u * HB_THREADS;
-          if (i < ne) tc[i] = t[u] + ac[i];
-        }
-      }
-    }
-  } else {
-    for (uint32_t i = tid; i < nf; i += HB_THREADS) {
-      const float v = acc[i];
-      if (v != 0.f) unsafeAtomicAdd(table + i, v);  // neighbouring lanes, neighbouring floats: the fast atomic shape
-    }
-  }
+  hb_flush_slice<C>(grad_grid + ((size_t)(uint32_t)offsets[level] + e0) * C, min(epb, hsize - e0), shared_slice,
+                    overwrite != 0, [&](const uint32_t i, const uint32_t ch) { return acc[i * C + ch]; });
 }
 
 // MSDF_HASH_BINNED_FORM=1 (read once per process) makes every binned call take the first form (count / scan / place /
@@ -839,35 +796,6 @@ hb2_accumulate_k(const int* __restrict__ ws, const Hb2Layout y, const int* __res
 static bool hb_force_first_form() {
   static const int v = [] { const char* e = getenv("MSDF_HASH_BINNED_FORM"); return (e && e[0] == '1') ? 1 : 0; }();
   return v != 0;
-}
-
-template <int C, int MODE>
-static int hb_run(const float* grad, const float* grad2, const float* inputs, const int* offsets,
-                  const float* gg_inputs, float* grad_grid, const uint32_t B, const uint32_t L, const float S,
-                  const uint32_t H, const uint64_t n_entries, void* workspace, const size_t workspace_bytes,
-                  hipStream_t st, const bool overwrite = false, const uint32_t pitch = 0) {
-  if (n_entries * C >= (1ull << 31) || (uint64_t)B * L * 8 >= (1ull << 31)) return MSDF_ERR_UNSUPPORTED;
-  int* ws = (int*)workspace;
-  const Hb2Layout y2 = hb2_layout(B, C, L, n_entries);
-  if (y2.ns_bound <= HB2_NS_MAX && !hb_force_first_form()) {
-    if (workspace == nullptr || workspace_bytes < y2.total_bytes || ((uintptr_t)workspace & 15)) return MSDF_ERR_ARG;
-    const size_t lds = (size_t)(y2.ns_bound + 1 + HB_THREADS) * sizeof(int);
-    hb2_place_k<C, MODE><<<dim3((unsigned)y2.n_wg, L), HB_THREADS, lds, st>>>(grad, grad2, inputs, offsets, gg_inputs, ws,
-                                                                             y2, B, S, H, overwrite ? grad_grid : nullptr, pitch);
-    hb2_accumulate_k<C><<<(unsigned)y2.work_max, HB_THREADS, 0, st>>>(ws, y2, offsets, L, grad_grid, overwrite ? 1 : 0);
-    return MSDF_OK;
-  }
-  if (pitch != 0) return MSDF_ERR_UNSUPPORTED;      // the first form reads level-major gradients only
-  if (overwrite && hipMemsetAsync(grad_grid, 0, (size_t)n_entries * C * sizeof(float), st) != hipSuccess) return MSDF_ERR_LAUNCH;
-  const HbLayout y = hb_layout(B, C, L, n_entries);
-  if (workspace == nullptr || workspace_bytes < y.total_bytes || ((uintptr_t)workspace & 15)) return MSDF_ERR_ARG;
-  const dim3 grid_pl((B + HB_PTS * HB_THREADS - 1) / (HB_PTS * HB_THREADS), L);
-  hb_setup_k<<<1, HB_THREADS, 0, st>>>(ws, y, offsets, L, C);
-  hb_count_k<C><<<grid_pl, HB_THREADS, 0, st>>>(inputs, offsets, ws, y, B, S, H);
-  hb_scan_k<<<1, 1024, 0, st>>>(ws, y, offsets, L, C, S, H);
-  hb_place_k<C, MODE><<<grid_pl, HB_THREADS, 0, st>>>(grad, grad2, inputs, offsets, gg_inputs, ws, y, B, S, H);
-  hb_accumulate_k<C><<<(unsigned)y.work_max, HB_THREADS, 0, st>>>(ws, y, grad_grid);
-  return MSDF_OK;
 }
 
 // ---- the one host launcher behind the seven table-gradient entry points of hashgrid.hip ----
@@ -880,6 +808,39 @@ struct HgTableGrad {                   // what to add into (or write to) the tab
   void* workspace;
   size_t workspace_bytes;
 };
+
+// the binned forms.  MODE of the place kernels: 0 first term only, 1 second only (its operand in the `grad` slot), 2 both
+template <int C, int MODE>
+static int hb_run(const HgTableGrad& t, const float* inputs, const int* offsets, float* grad_grid, const uint32_t B,
+                  const uint32_t L, const float S, const uint32_t H, hipStream_t st) {
+  if (t.n_entries * C >= (1ull << 31) || (uint64_t)B * L * 8 >= (1ull << 31)) return MSDF_ERR_UNSUPPORTED;
+  const float* grad = (MODE == 1) ? t.grad_second : t.grad_first;
+  const float* grad2 = (MODE == 2) ? t.grad_second : nullptr;
+  int* ws = (int*)t.workspace;
+  const auto workspace_holds = [&](const size_t bytes) {
+    return t.workspace != nullptr && t.workspace_bytes >= bytes && !((uintptr_t)t.workspace & 15);
+  };
+  const Hb2Layout y2 = hb2_layout(B, C, L, t.n_entries);
+  if (y2.ns_bound <= HB2_NS_MAX && !hb_force_first_form()) {
+    if (!workspace_holds(y2.total_bytes)) return MSDF_ERR_ARG;
+    const size_t lds = (size_t)(y2.ns_bound + 1 + HB_THREADS) * sizeof(int);
+    hb2_place_k<C, MODE><<<dim3((unsigned)y2.n_wg, L), HB_THREADS, lds, st>>>(
+        grad, grad2, inputs, offsets, t.gg_inputs, ws, y2, B, S, H, t.overwrite ? grad_grid : nullptr, t.pitch);
+    hb2_accumulate_k<C><<<(unsigned)y2.work_max, HB_THREADS, 0, st>>>(ws, y2, offsets, L, grad_grid, t.overwrite ? 1 : 0);
+    return MSDF_OK;
+  }
+  if (t.pitch != 0) return MSDF_ERR_UNSUPPORTED;      // the first form reads level-major gradients only
+  if (t.overwrite && hipMemsetAsync(grad_grid, 0, (size_t)t.n_entries * C * sizeof(float), st) != hipSuccess) return MSDF_ERR_LAUNCH;
+  const HbLayout y = hb_layout(B, C, L, t.n_entries);
+  if (!workspace_holds(y.total_bytes)) return MSDF_ERR_ARG;
+  const dim3 grid_pl((B + HB_PTS * HB_THREADS - 1) / (HB_PTS * HB_THREADS), L);
+  hb_setup_k<<<1, HB_THREADS, 0, st>>>(ws, y, offsets, L, C);
+  hb_count_k<C><<<grid_pl, HB_THREADS, 0, st>>>(inputs, offsets, ws, y, B, S, H);
+  hb_scan_k<<<1, 1024, 0, st>>>(ws, y, offsets, L, C, S, H);
+  hb_place_k<C, MODE><<<grid_pl, HB_THREADS, 0, st>>>(grad, grad2, inputs, offsets, t.gg_inputs, ws, y, B, S, H);
+  hb_accumulate_k<C><<<(unsigned)y.work_max, HB_THREADS, 0, st>>>(ws, y, grad_grid);
+  return MSDF_OK;
+}
 
 // Refusals, in this order, all before anything is launched (the table gradient is untouched by a refused call):
 // grad_grid == NULL -> ARG;  B == 0 -> OK ("=": the table is zeroed);  no term, a NULL operand or pitch < L C -> ARG;
@@ -901,13 +862,6 @@ static int hg_table_gradient(const HgTableGrad& t, const float* inputs, const in
     return second ? hg_launch_scatter<C, true>(t.grad_second, inputs, offsets, t.gg_inputs, grad_grid, B, L, S, H, st)
                   : hg_launch_scatter<C, false>(t.grad_first, inputs, offsets, nullptr, grad_grid, B, L, S, H, st);
   }
-  // MODE of the place kernels: 0 first term only, 1 second only (its operand in the `grad` slot), 2 both
-  if (first && second)
-    return hb_run<C, 2>(t.grad_first, t.grad_second, inputs, offsets, t.gg_inputs, grad_grid, B, L, S, H, t.n_entries,
-                        t.workspace, t.workspace_bytes, st, t.overwrite, t.pitch);
-  if (second)
-    return hb_run<C, 1>(t.grad_second, nullptr, inputs, offsets, t.gg_inputs, grad_grid, B, L, S, H, t.n_entries,
-                        t.workspace, t.workspace_bytes, st, t.overwrite, t.pitch);
-  return hb_run<C, 0>(t.grad_first, nullptr, inputs, offsets, nullptr, grad_grid, B, L, S, H, t.n_entries, t.workspace,
-                      t.workspace_bytes, st, t.overwrite, t.pitch);
+  const auto run = (first && second) ? hb_run<C, 2> : second ? hb_run<C, 1> : hb_run<C, 0>;
+  return run(t, inputs, offsets, grad_grid, B, L, S, H, st);
 }

@@ -16,36 +16,36 @@
 
 #define HG_THREADS 256
 
-__device__ __forceinline__ uint32_t hg_index(const uint32_t px, const uint32_t py, const uint32_t pz,
-                                             const uint32_t hashmap_size, const uint32_t resolution) {
-  // dense while the running stride still fits the level, hashed otherwise (cu:54-72)
-  uint32_t stride = 1, index = 0;
-  const uint32_t p[3] = {px, py, pz};
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (stride <= hashmap_size) {
-      index += p[d] * stride;
-      stride *= resolution;
-    }
-  }
-  if (stride > hashmap_size) index = px ^ (py * 2654435761u) ^ (pz * 805459861u);
-  return (index < hashmap_size) ? index : index % hashmap_size;     // same value; dense levels skip the division
-}
-
 struct HgCell {
   float scale;
-  uint32_t res, hsize;
   uint32_t gx, gy, gz;
   float sx, sy, sz;       // smoothstep(frac)
   float dx, dy, dz;       // smoothstep'(frac)
   bool oob;
 };
 
+// scale and resolution of a level, on the host as in the kernels (hg_small_levels sizes the LDS tables with it)
+struct HgRes {
+  float scale;
+  uint32_t res;
+};
+__host__ __device__ __forceinline__ HgRes hg_resolution(const uint32_t level, const float S, const uint32_t H) {
+  HgRes r;
+  // exp2f(level * S) as the correctly rounded float (device exp2f is only ~1 ulp; one ulp of scale moves a
+  // fine-level sample by 1e-4 of a cell)
+  r.scale = (float)exp2((double)((float)level * S)) * (float)H - 1.0f;
+  r.res = (uint32_t)ceilf(r.scale) + 1u;
+  return r;
+}
+
 // per-level constants (scale, resolution, table size): uniform over a workgroup of the level-major launches.
-// The index form of cu:54-72 is decided here, once per level instead of once per corner: `dense` = the running
-// stride never exceeds the table (index = x + y res + z res^2), otherwise the xor hash; `mask` = hsize - 1 when
-// the table size is a power of two (every hashed level of the reference's configurations: the modulo becomes an
-// AND instead of a ~40-instruction integer division per corner).
+// The reference decides the index form per corner (cu:54-72): a loop over the three axes adds p[d] * stride and
+// multiplies the 32-bit running stride by the resolution while that stride still fits the level (stride <= hsize);
+// if the stride has outgrown the level at the end, the index is the xor hash px ^ py * 2654435761 ^ pz * 805459861
+// instead; either way it is taken modulo hsize.  The same loop runs here with the coordinates left out, once per
+// level instead of once per corner: `dense` = the running stride never exceeds the table (index = x + y res +
+// z res^2), otherwise the xor hash; `mask` = hsize - 1 when the table size is a power of two (every hashed level of
+// the reference's configurations: the modulo becomes an AND instead of a ~40-instruction integer division per corner).
 struct HgLevel {
   float scale;
   uint32_t res, hsize;
@@ -56,11 +56,10 @@ __device__ __forceinline__ HgLevel hg_level(const int* __restrict__ offsets, con
                                             const uint32_t H) {
   HgLevel v;
   v.hsize = (uint32_t)(offsets[level + 1] - offsets[level]);
-  // exp2f(level * S) as the correctly rounded float (device exp2f is only ~1 ulp; one ulp of scale moves a
-  // fine-level sample by 1e-4 of a cell)
-  v.scale = (float)exp2((double)((float)level * S)) * (float)H - 1.0f;
-  v.res = (uint32_t)ceilf(v.scale) + 1u;
-  // the loop of hg_index with the coordinates left out: which strides are taken, and whether the last one fits
+  const HgRes r = hg_resolution(level, S, H);
+  v.scale = r.scale;
+  v.res = r.res;
+  // which strides are taken, and whether the last one fits
   uint32_t stride = 1;
   v.s1 = v.s2 = 0;
   if (stride <= v.hsize) stride *= v.res;                        // d = 0 (stride 1)
@@ -71,22 +70,20 @@ __device__ __forceinline__ HgLevel hg_level(const int* __restrict__ offsets, con
   return v;
 }
 
-// hg_index with the level's decisions taken from HgLevel (same value for every input)
+// the table entry of grid point (px, py, pz): the reference's index with the level's decisions taken from HgLevel
 __device__ __forceinline__ uint32_t hg_index_lv(const HgLevel& lv, const uint32_t px, const uint32_t py,
                                                 const uint32_t pz) {
   uint32_t index;
   if (lv.dense) index = px + py * lv.s1 + pz * lv.s2;
   else index = px ^ (py * 2654435761u) ^ (pz * 805459861u);
   if (lv.mask) return index & lv.mask;
-  return (index < lv.hsize) ? index : index % lv.hsize;
+  return (index < lv.hsize) ? index : index % lv.hsize;     // same value; dense levels skip the division
 }
 
 __device__ __forceinline__ HgCell hg_locate_xyz(const float x, const float y, const float z, const HgLevel& lv) {
   HgCell c;
   c.oob = (x < 0.f || x > 1.f || y < 0.f || y > 1.f || z < 0.f || z > 1.f);
-  c.hsize = lv.hsize;
   c.scale = lv.scale;
-  c.res = lv.res;
   float px = x * c.scale, py = y * c.scale, pz = z * c.scale;
   const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
   c.gx = (uint32_t)fx; c.gy = (uint32_t)fy; c.gz = (uint32_t)fz;
@@ -100,11 +97,55 @@ __device__ __forceinline__ HgCell hg_locate(const float* __restrict__ inputs, co
   return hg_locate_xyz(inputs[(size_t)b * 3 + 0], inputs[(size_t)b * 3 + 1], inputs[(size_t)b * 3 + 2], lv);
 }
 
-__device__ __forceinline__ HgCell hg_locate(const float* __restrict__ inputs, const int* __restrict__ offsets,
-                                            const uint32_t b, const uint32_t level, const float S,
-                                            const uint32_t H) {
-  return hg_locate(inputs, hg_level(offsets, level, S, H), b);
+// Corner k of a cell is the grid point (gx + (k & 1), gy + ((k >> 1) & 1), gz + ((k >> 2) & 1)): its table entry ...
+__device__ __forceinline__ uint32_t hg_corner_index(const HgLevel& lv, const HgCell& c, const int k) {
+  return hg_index_lv(lv, c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1));
 }
+
+// ... and what it weighs, from the per-axis weights wx, wy, wz = {1 - smoothstep, smoothstep} of the cell.  k is a
+// compile-time constant wherever these functions are called (unrolled loops), so the arrays are registers.  The
+// association and order of every product and sum here is what the values of the table gradient are made of:
+// hashgrid.o is built with -ffp-contract=off.
+// w_k, the trilinear weight                                           (kernel_grid, kernel_grid_backward, cu:257-343)
+__device__ __forceinline__ float hg_corner_weight(const float (&wx)[2], const float (&wy)[2], const float (&wz)[2],
+                                                  const int k) {
+  return wx[k & 1] * wy[(k >> 1) & 1] * wz[(k >> 2) & 1];
+}
+// the second-order coefficient: sum over axes of +/- the other axes' weights * q_d, q_d = gg_d * smoothstep'_d * scale
+//                                                                     (kernel_grid_second_backward_embedding, cu:431-595)
+__device__ __forceinline__ float hg_corner_coefficient(const float (&wx)[2], const float (&wy)[2], const float (&wz)[2],
+                                                       const float q0, const float q1, const float q2, const int k) {
+  const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
+  return (bx ? 1.f : -1.f) * wy[by] * wz[bz] * q0 + (by ? 1.f : -1.f) * wx[bx] * wz[bz] * q1 +
+         (bz ? 1.f : -1.f) * wx[bx] * wy[by] * q2;
+}
+// what one channel adds to corner k of the table gradient, from wk = hg_corner_weight and qk = hg_corner_coefficient
+// formed once per corner (the one a MODE does not read is dead code).  MODE 0: w_k * grad;  MODE 1: coefficient * grad;
+// MODE 2: w_k * grad + coefficient * grad2, both table gradients in one pass
+template <int MODE>
+__device__ __forceinline__ float hg_corner_value(const float wk, const float qk, const float g1, const float g2) {
+  if (MODE == 0) return wk * g1;
+  if (MODE == 1) return qk * g1;
+  return wk * g1 + qk * g2;
+}
+// the operands of the three functions above for one cell; gg: the point's three gg_inputs, NULL where no second-order
+// term is formed.  (hb2_place_k keeps them as plain locals: see there.)
+struct HgCorners {
+  float wx[2], wy[2], wz[2];
+  float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+  __device__ __forceinline__ HgCorners(const HgCell& c, const float* __restrict__ gg)
+      : wx{1.f - c.sx, c.sx}, wy{1.f - c.sy, c.sy}, wz{1.f - c.sz, c.sz} {
+    if (gg != nullptr) {
+      q0 = gg[0] * c.dx * c.scale;
+      q1 = gg[1] * c.dy * c.scale;
+      q2 = gg[2] * c.dz * c.scale;
+    }
+  }
+  __device__ __forceinline__ float weight(const int k) const { return hg_corner_weight(wx, wy, wz, k); }
+  __device__ __forceinline__ float coefficient(const int k) const {
+    return hg_corner_coefficient(wx, wy, wz, q0, q1, q2, k);
+  }
+};
 
 // ---------------------------------------------------------------------------
 // forward
@@ -129,7 +170,7 @@ __device__ __forceinline__ void hg_forward_cell(const HgCell& c, const float* __
   float v[8][C];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const uint32_t idx = hg_index_lv(lv, c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1));
+    const uint32_t idx = hg_corner_index(lv, c, k);
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) v[k][ch] = table[(size_t)idx * C + ch];
   }
@@ -139,7 +180,7 @@ __device__ __forceinline__ void hg_forward_cell(const HgCell& c, const float* __
   for (int ch = 0; ch < C; ++ch) res[ch] = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const float w = wx[k & 1] * wy[(k >> 1) & 1] * wz[(k >> 2) & 1];
+    const float w = hg_corner_weight(wx, wy, wz, k);
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) res[ch] += w * v[k][ch];
   }

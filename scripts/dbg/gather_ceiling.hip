@@ -111,7 +111,7 @@ replay_k(const float* __restrict__ x, const float inv_divide, const v2f* __restr
     const v2f* t = grid + (size_t)(uint32_t)offsets[level];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const v2f v = t[hg_index_lv(lv, c.gx + (k & 1), c.gy + ((k >> 1) & 1), c.gz + ((k >> 2) & 1))];
+      const v2f v = t[hg_corner_index(lv, c, k)];
       acc += v;
       a2 += v.x - v.y;
     }

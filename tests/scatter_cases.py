@@ -32,6 +32,9 @@ K = dict(
     HB_RANK_SHIFT=19,          # first form: (index | rank << 19) needs hsize <= 2^19
     HB2_NS_MAX=8192,           # second form: taken when no more slices than this (otherwise the first form)
     HB2_TILE=256,              # second form: runs per pass of the accumulate kernel
+    HG_LDS_MAX_BYTES=100 * 1024,   # atomic form: a level whose dense table fits this is accumulated in LDS
+    HG_LDS_WGS=128,            # ... by this many workgroups per level
+    HG_LDS_THREADS=1024,
 )
 WG_POINTS = K['HB_PTS'] * K['HB_THREADS']
 ROW, WAVE = 16, 64             # runs of equal cells are merged inside 16-lane rows of a 64-lane wave
@@ -91,6 +94,27 @@ def structure(geo, B, C):
     return dict(n_wg=n_wg, last_wg_partial=B % WG_POINTS != 0, ns_bound=ns_bound,
                 second_form=ns_bound <= K['HB2_NS_MAX'], levels=levels,
                 items=sum(v['items'] for v in levels), work_max=total_slices + L + L * n_wg)
+
+
+def atomic_structure(geo, B, C):
+    """What hg_small_levels and hg_scatter_lds_kernel decide for the atomic form: the leading levels whose DENSE table
+    (resolution^3 entries of C floats) fits HG_LDS_MAX_BYTES go to the LDS kernel, with an LDS table of `lds_floats`
+    floats (the largest of them, rounded up to 256 bytes); inside it a level whose real table (hsize * C floats) is
+    larger than that falls back to direct atomics."""
+    n_small, nbytes = 0, 0
+    for l in range(geo['L']):
+        _, res = hg.level_scale(geo, l)
+        b = res ** 3 * C * 4
+        if b > K['HG_LDS_MAX_BYTES']:
+            break
+        nbytes = max(nbytes, b)
+        n_small += 1
+    lds_floats = ((nbytes + 255) & ~255) // 4
+    sizes = [geo['offsets'][l + 1] - geo['offsets'][l] for l in range(n_small)]
+    per = _cdiv(B, K['HG_LDS_WGS'])
+    return dict(n_small=n_small, lds_floats=lds_floats, fits=[s * C <= lds_floats for s in sizes],
+                kinds=[level_kind(geo, l) for l in range(n_small)], per=per,
+                empty_wgs=sum(1 for w in range(K['HG_LDS_WGS']) if w * per >= B))
 
 
 def first_form_chunks(geo, x, C):
@@ -265,6 +289,12 @@ def first_form_geometry(C, which):
 
 FIRST_FORM_CASES = [(C, which) for C in (1, 2, 8) for which in ('large', 'side')]
 
+# 2f, the atomic form's LDS kernel (H = 17, resolution 17: every level is "small"): the dense level fills the LDS table
+# exactly | a dense index with slack, larger than the LDS table (direct atomics from inside the kernel) | tiny, modulo
+N_EXP_LDS = 4
+SIZES_LDS_ATOMIC = [17 ** 3, 8192, 25]
+LDS_ATOMIC_CHANNELS = (1, 2, 4)                        # C = 8: 157 KB, not an LDS level
+
 
 _CACHE = {}
 
@@ -292,6 +322,10 @@ def case_second_pass():
 def case_first_form(C, which):
     n, sizes = first_form_geometry(C, which)
     return cached_case('first', 400 + C, n, C, sizes, B_MULTI)
+
+
+def case_lds_atomic(C):
+    return cached_case('lds', 500 + C, N_EXP_LDS, C, SIZES_LDS_ATOMIC, B_MULTI)
 
 
 # ---- 2e: realistic geometry (S != 0), random float operands: not exact, compared per level ----

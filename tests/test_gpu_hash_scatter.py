@@ -181,6 +181,29 @@ def test_first_form_small_and_exact():
     assert '%d passed' % len(sc.FIRST_FORM_CASES) in r.stdout, r.stdout[-500:]
 
 
+# ---- f: the atomic form's LDS kernel ----
+@pytest.mark.parametrize('C', sc.LDS_ATOMIC_CHANNELS)
+def test_atomic_lds_kernel_exact(C):
+    """H = 17: every level's dense table fits the LDS budget, so the atomic entry points send all three to
+    hg_scatter_lds_kernel -- a dense level that fills the LDS table, a level larger than it (direct atomics from inside
+    the kernel) and a tiny modulo-hashed one; the last three of the 128 workgroups of a level have no points.  Into zeros
+    and into a prefilled table."""
+    case = sc.case_lds_atomic(C)
+    _assert_certificate(case)
+    a = sc.atomic_structure(case.geo, case.B, C)
+    assert a['n_small'] == 3 and a['fits'] == [True, False, True] and a['kinds'] == ['dense', 'dense', 'modulo']
+    assert a['empty_wgs'] == 3
+    forms = _forms(case, ('atomic', 'atomic_second'))
+    g = torch.Generator().manual_seed(17 + C)
+    prefill = torch.randint(-3, 4, (case.geo['n_entries'], C), generator=g).float()
+    for start, what in ((None, ''), (prefill, ' into a prefilled table')):
+        r = _run(case, forms, guard=3, **({} if start is None else {'prefill': start.cuda()}))
+        for f in forms:
+            want = _want(case, f) if start is None else start.double() + _want(case, f)
+            _assert_exact(case, r[f], want, f + what)
+            assert bool((r[f + '_guard'] == 1234.5).all()), f
+
+
 # ---- e: realistic geometry against the float64 oracle, per level ----
 @pytest.mark.parametrize('index', range(len(sc.REAL_CONFIGS)))
 def test_realistic_geometry_against_float64_oracle_per_level(index, errlog):

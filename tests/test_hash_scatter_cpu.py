@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXACT_CASES = [('entry-C%d' % C, lambda C=C: sc.case_every_entry_point(C)) for C in (1, 2, 4, 8)] + \
               [('edge-B%d' % B, lambda B=B: sc.case_batch_edge(B)) for B in sc.BATCH_EDGES] + \
               [('second-pass', sc.case_second_pass)] + \
-              [('first-C%d-%s' % (C, w), lambda C=C, w=w: sc.case_first_form(C, w)) for C, w in sc.FIRST_FORM_CASES]
+              [('first-C%d-%s' % (C, w), lambda C=C, w=w: sc.case_first_form(C, w)) for C, w in sc.FIRST_FORM_CASES] + \
+              [('lds-atomic-C%d' % C, lambda C=C: sc.case_lds_atomic(C)) for C in sc.LDS_ATOMIC_CHANNELS]
 
 
 @pytest.fixture(params=EXACT_CASES, ids=[n for n, _ in EXACT_CASES])
@@ -25,10 +26,12 @@ def case(request):
 
 def test_constants_are_those_of_hash_scatter_h():
     text = open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'hash_scatter.h')).read()
-    for name in ('HB_SLICE_FLOATS', 'HB_CHUNK', 'HB_THREADS', 'HB_PTS', 'HB_MAX_SLICES', 'HB2_NS_MAX', 'HB2_TILE'):
-        m = re.search(r'#define %s (\d+)' % name, text)
+    for name in ('HB_SLICE_FLOATS', 'HB_CHUNK', 'HB_THREADS', 'HB_PTS', 'HB_MAX_SLICES', 'HB_RANK_SHIFT', 'HB2_NS_MAX',
+                 'HB2_TILE', 'HG_LDS_WGS', 'HG_LDS_THREADS'):
+        m = re.search(r'#define %s (\d+)\b' % name, text)
         assert m and int(m.group(1)) == sc.K[name], name
-    assert 'rank << %d' % sc.K['HB_RANK_SHIFT'] in text and 'lv.hsize <= (1u << %d)' % sc.K['HB_RANK_SHIFT'] in text
+    m = re.search(r'#define HG_LDS_MAX_BYTES \((\d+) \* (\d+)\)', text)
+    assert m and int(m.group(1)) * int(m.group(2)) == sc.K['HG_LDS_MAX_BYTES']
 
 
 def test_exactness_certificate_holds(case):
@@ -142,6 +145,22 @@ def test_first_form_case_reaches_its_branches(C, which):
             assert lv[2]['ns'] > sc.K['HB_MAX_SLICES'] and not lv[2]['count_local']
     else:
         assert lv[0]['kind'] == 'dense' and lv[1]['kind'] == 'modulo'
+
+
+@pytest.mark.parametrize('C', sc.LDS_ATOMIC_CHANNELS)
+def test_lds_atomic_case_reaches_its_branches(C):
+    """All three levels go to hg_scatter_lds_kernel: the dense one fills the LDS table, the second is larger than it (the
+    kernel's fallback to direct atomics), the third is modulo-hashed inside LDS; the last workgroups have no points."""
+    case = sc.case_lds_atomic(C)
+    a = sc.atomic_structure(case.geo, case.B, C)
+    assert a['n_small'] == 3 == case.geo['L'] and a['fits'] == [True, False, True]
+    assert a['kinds'] == ['dense', 'dense', 'modulo']
+    assert 17 ** 3 * C <= a['lds_floats'] < 17 ** 3 * C + 64 and a['lds_floats'] * 4 <= sc.K['HG_LDS_MAX_BYTES']
+    assert a['per'] == 25 and a['empty_wgs'] == 3
+    # C = 8 would not reach the kernel at all
+    assert sc.atomic_structure(sc.make_geo(sc.N_EXP_LDS, 8, sc.SIZES_LDS_ATOMIC), case.B, 8)['n_small'] == 0
+    # ... and the cases of the other tests never do (H = 65: a dense table of 1.1 MB)
+    assert sc.atomic_structure(sc.case_every_entry_point(C).geo, sc.B_MULTI, C)['n_small'] == 0
 
 
 def test_realistic_cases_have_runs_and_a_measured_tolerance():
