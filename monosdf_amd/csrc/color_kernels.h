@@ -2,14 +2,16 @@
 #pragma once
 #include "mlp_core.h"
 
-typedef msdf_color_fwd_args_t ColorFwdArgs;
+// The output layer behind a hidden one as dot products over the register-resident activation (1) or as a matrix product
+// like the other layers (0: variants built for timing), forward and backward
+#ifndef MSDF_DOT_FWD
+#define MSDF_DOT_FWD 1
+#endif
+#ifndef MSDF_DOT_BWD
+#define MSDF_DOT_BWD 1
+#endif
 
-template <class Core>
-__device__ __forceinline__ int wave_point(int& q) {
-  const int lane = lane_id();
-  q = lane >> 4;
-  return blockIdx.x * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane & 15);
-}
+typedef msdf_color_fwd_args_t ColorFwdArgs;
 
 // misc block in slot layout: idr: [x(3) | PE(v) | n(3)], nerf: [PE(v)]; then code tiles
 __device__ __forceinline__ void color_misc_tiles(v4f (&m)[5], const msdf_plan_t& plan, const float* __restrict__ x,
@@ -53,37 +55,25 @@ __device__ __forceinline__ void color_misc_tiles(v4f (&m)[5], const msdf_plan_t&
 
 
 // ---------------------------------------------------------------------------
-// Product hooks (protocol: mlp_core.h, NoHooks); lane pointers as in sdf_kernels.h.  kt == 0 disables a hook.
+// Product hooks (protocol, lane pointers and the shared pieces: mlp_core.h, NoHooks).  kt == 0 disables a hook.
 // ---------------------------------------------------------------------------
-struct ColorPending {
-  float* dst;
-  v4f s0, s1;
-  int t0, n;
-  __device__ __forceinline__ void issue() {
-    if (n > 0) *(v4f*)(dst + 16 * t0) = s0;
-    if (n > 1) *(v4f*)(dst + 16 * t0 + 16) = s1;
-    n = 0;
-  }
-};
 
 // forward: h = relu(a) in place, saved to H (input of the next layer)
 struct ReluSaveHooks {
   int kt;
   bool save;
-  ColorPending st;
-  __device__ __forceinline__ ReluSaveHooks(float* H, const int kt_, const bool save_) : kt(kt_), save(save_) {
-    st.dst = H; st.n = 0; st.t0 = 0;
-  }
+  PendingStores st;
+  __device__ __forceinline__ ReluSaveHooks(float* H, const int kt_, const bool save_) : kt(kt_), save(save_), st(H) {}
   __device__ __forceinline__ void pre(const int, const int) { st.issue(); }
   __device__ __forceinline__ void post(const int o0, const int o1, const bool pair, v4f& a0, v4f& a1) {
     if (o0 < kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[r] = fmaxf(a0[r], 0.f);
-      st.s0 = a0; st.t0 = o0; st.n = save ? 1 : 0;
+      st.keep(o0, a0, save);
       if (pair && o1 < kt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) a1[r] = fmaxf(a1[r], 0.f);
-        st.s1 = a1; st.n = save ? 2 : 0;
+        st.keep_pair(a1, save);
       }
     }
   }
@@ -95,10 +85,8 @@ struct ReluMaskHooks {
   const float* H;
   int kt;
   v4f h0, h1;
-  ColorPending st;
-  __device__ __forceinline__ ReluMaskHooks(const float* H_, float* AB, const int kt_) : H(H_), kt(kt_) {
-    st.dst = AB; st.n = 0; st.t0 = 0;
-  }
+  PendingStores st;
+  __device__ __forceinline__ ReluMaskHooks(const float* H_, float* AB, const int kt_) : H(H_), kt(kt_), st(AB) {}
   __device__ __forceinline__ void pre(const int o0, const int o1) {
     st.issue();
     if (kt > 0) {
@@ -110,11 +98,11 @@ struct ReluMaskHooks {
     if (o0 < kt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[r] = (h0[r] > 0.f) ? a0[r] : 0.f;
-      st.s0 = a0; st.t0 = o0; st.n = 1;
+      st.keep(o0, a0);
       if (pair && o1 < kt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) a1[r] = (h1[r] > 0.f) ? a1[r] : 0.f;
-        st.s1 = a1; st.n = 2;
+        st.keep_pair(a1);
       }
     }
   }
@@ -124,8 +112,8 @@ struct ReluMaskHooks {
 template <class Core>
 __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, const ColorFwdArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  int q;
-  const int pt = wave_point<Core>(q);
+  const int q = lane_quarter();
+  const int pt = lane_point<Core>(blockIdx.x);
   const bool valid = pt < a.P;
   const int ptc = valid ? pt : a.P - 1;
   const int ray = ptc / a.spr;
@@ -137,13 +125,8 @@ __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, cons
   const msdf_layer_t U0 = plan.layer[0];
 #pragma unroll
   for (int t = 0; t < MT; ++t)
-    in[t] = (t < U0.kt) ? *(const v4f*)(a.feat + (size_t)ptc * (16 * U0.kt) + 16 * t + 4 * q) : V4ZERO;
-  if constexpr (Core::BIAS_IN_HOOKS) {
-    Core::gemm_bias(U0.ktp, acc, in, U0.ot, (const wvec*)a.wpack + U0.wf_off, lds, NoHooks(), a.bpack + U0.bias_off + 4 * q);
-  } else {
-    load_bias(acc, a.bpack + U0.bias_off, U0.ot, q);
-    Core::gemm(U0.ktp, acc, in, U0.ot, (const wvec*)a.wpack + U0.wf_off, lds, NoHooks());
-  }
+    in[t] = (t < U0.kt) ? *(const v4f*)lane_row(a.feat, 0, 0, ptc, U0.kt, q, t) : V4ZERO;
+  Core::gemm_bias(U0.ktp, acc, in, U0.ot, (const wvec*)a.wpack + U0.wf_off, lds, NoHooks(), a.bpack + U0.bias_off + 4 * q);
   // ---- first layer, misc part (same accumulators)
   {
     v4f m[5];
@@ -152,33 +135,24 @@ __device__ __forceinline__ void color_forward_body(const msdf_plan_t& plan, cons
     if (a.save) {
 #pragma unroll
       for (int t = 0; t < 5; ++t)
-        if (t < misc_tiles) *(v4f*)(a.MISC + (size_t)pt * (16 * misc_tiles) + 16 * t + 4 * q) = m[t];
+        if (t < misc_tiles) *(v4f*)lane_row(a.MISC, 0, 0, pt, misc_tiles, q, t) = m[t];
     }
   }
   // every product but the last hands relu(output) to the next layer through its hooks (saved to H on the way)
   auto next_hooks = [&](const int u) {     // hooks of the product that feeds unit u (u >= nu: none)
     const msdf_layer_t Ln = plan.layer[u < nu ? u : 0];
-    return ReluSaveHooks(a.H + (size_t)Ln.hpre * Pp + (size_t)pt * (16 * Ln.kt) + 4 * q, u < nu ? Ln.kt : 0,
-                         a.save != 0);
+    return ReluSaveHooks(lane_row(a.H, Ln.hpre, Pp, pt, Ln.kt, q), u < nu ? Ln.kt : 0, a.save != 0);
   };
   const msdf_layer_t U1 = plan.layer[1];
   Core::gemm(U1.ktp, acc, in, U1.ot, (const wvec*)a.wpack + U1.wf_off, lds, next_hooks(2));
   // ---- hidden layers
-#ifndef MSDF_DOT_FWD
-#define MSDF_DOT_FWD 1
-#endif
   const bool dot_out = MSDF_DOT_FWD && nu >= 3;             // the output layer behind a hidden one: three dot products, not a product
   for (int u = 2; u < (dot_out ? nu - 1 : nu); ++u) {
     const msdf_layer_t L = plan.layer[u];
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = (t < L.kt) ? acc[t] : V4ZERO;
-    if constexpr (Core::BIAS_IN_HOOKS) {
-      Core::gemm_bias(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, next_hooks(u + 1),
-                      a.bpack + L.bias_off + 4 * q);
-    } else {
-      load_bias(acc, a.bpack + L.bias_off, L.ot, q);
-      Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, next_hooks(u + 1));
-    }
+    Core::gemm_bias(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, next_hooks(u + 1),
+                    a.bpack + L.bias_off + 4 * q);
   }
   // ---- output layer: rgb_c = w_c . relu(h) + b_c over the register-resident activation (a 16-row matrix tile
   // with 13 rows of zeros would be one dependent chain of 64 matrix instructions behind a weight chunk of its own)
@@ -215,8 +189,8 @@ typedef msdf_color_bwd_args_t ColorBwdArgs;
 template <class Core>
 __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, const ColorBwdArgs& a, void* lds) {
   typedef typename Core::wvec wvec;
-  int q;
-  const int pt = wave_point<Core>(q);
+  const int q = lane_quarter();
+  const int pt = lane_point<Core>(blockIdx.x);
   const bool valid = pt < a.P;
   const size_t Pp = (size_t)a.P_pad;
   const int nu = plan.n_layers;
@@ -239,23 +213,20 @@ __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, con
     if (q != 0) ab = V4ZERO;                  // slots 0..2 sit in tile 0, quarter 0
     in[0] = ab;
     const msdf_layer_t LL = plan.layer[nu - 1];
-    float* ABl = a.AB + (size_t)LL.abpre * Pp + (size_t)pt * (16 * LL.ot) + 4 * q;
+    float* ABl = lane_row(a.AB, LL.abpre, Pp, pt, LL.ot, q);
     *(v4f*)ABl = ab;
   }
   // ---- output layer behind a hidden one: h-bar = sum_c a-bar_c w_c as an outer product over the activation's slots
   // (the 3-row matrix product was 8 weight chunks of 8 matrix instructions each), masked and stored like a hook does
-#ifndef MSDF_DOT_BWD
-#define MSDF_DOT_BWD 1
-#endif
   const bool dot_out = MSDF_DOT_BWD && nu >= 3;
   if (dot_out) {
     const msdf_layer_t L = plan.layer[nu - 1];
     const float a0 = ab0, a1 = ab1, a2 = ab2;
     const float* w = a.bpack + plan.wsdf_off + 4 * q;
     const int ld = 16 * L.kt;
-    const float* Hl = a.H + (size_t)L.hpre * Pp + (size_t)pt * (16 * L.kt) + 4 * q;
+    const float* Hl = lane_row(a.H, L.hpre, Pp, pt, L.kt, q);
     const msdf_layer_t Lp = plan.layer[(nu - 2 == 1) ? 0 : nu - 2];
-    float* ABp = a.AB + (size_t)Lp.abpre * Pp + (size_t)pt * (16 * Lp.ot) + 4 * q;
+    float* ABp = lane_row(a.AB, Lp.abpre, Pp, pt, Lp.ot, q);
     const int ktl = L.kt - 1;
     v4f hh[MT];
 #pragma unroll
@@ -285,8 +256,8 @@ __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, con
     // its hooks mask it with the saved activation and store it as a-bar of that unit
     const msdf_layer_t Lp = plan.layer[(u - 1 == 1) ? 0 : u - 1];
     Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
-               ReluMaskHooks(a.H + (size_t)L.hpre * Pp + (size_t)pt * (16 * L.kt) + 4 * q,
-                             a.AB + (size_t)Lp.abpre * Pp + (size_t)pt * (16 * Lp.ot) + 4 * q, L.kt));
+               ReluMaskHooks(lane_row(a.H, L.hpre, Pp, pt, L.kt, q), lane_row(a.AB, Lp.abpre, Pp, pt, Lp.ot, q),
+                             L.kt));
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = (t < L.kt) ? acc[t] : V4ZERO;
   }
@@ -297,7 +268,7 @@ __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, con
   if (valid) {
 #pragma unroll
     for (int t = 0; t < MT; ++t)
-      if (t < U0.kt) *(v4f*)(a.g_feat + (size_t)pt * (16 * U0.kt) + 16 * t + 4 * q) = acc[t];
+      if (t < U0.kt) *(v4f*)lane_row(a.g_feat, 0, 0, pt, U0.kt, q, t) = acc[t];
   }
   const msdf_layer_t U1 = plan.layer[1];
   zero_tiles(acc);
@@ -305,7 +276,7 @@ __device__ __forceinline__ void color_backward_body(const msdf_plan_t& plan, con
   if (valid) {
 #pragma unroll
     for (int t = 0; t < 5; ++t)
-      if (t < misc_tiles) *(v4f*)(a.g_misc + (size_t)pt * (16 * misc_tiles) + 16 * t + 4 * q) = acc[t];
+      if (t < misc_tiles) *(v4f*)lane_row(a.g_misc, 0, 0, pt, misc_tiles, q, t) = acc[t];
     if (a.g_nrm != nullptr && plan.mode == 1) {
       // misc slots of mode idr: [x (3) | PE(view) (3 + 6 n_freqs) | normal (3)] -- the normal's gradient once more
       // as a dense [P,3] row, so the caller does not have to copy the strided columns out

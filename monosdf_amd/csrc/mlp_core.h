@@ -90,6 +90,31 @@ struct NoHooks {
   __device__ __forceinline__ void drain() {}
 };
 
+// What the implementers of the protocol share.  Their pointers are LANE pointers into a row of the lane's point
+// (lane_row() below): tile t of the row sits at p + 16 t.  The clamped tile load of pre(),
+// p + 16 * (o < ot ? o : ot - 1), stays written out in every hook: as a function the compiler turns the clamp into a
+// min in place of a select and the sweep kernels' instruction streams and spills move.
+//
+// Results post() wants stored wait here, in registers, until the next pre() or drain() issues them.  post() keeps the
+// first tile of its pair (on == false: transformed in place only, nothing to store) and then, if there is one, the
+// second.  The tiles are taken by reference: by value the hooks' registers are allocated in another order and the
+// bf16x6 backward kernel spills 36 more.
+struct PendingStores {
+  float* dst;
+  v4f s0, s1;
+  int t0, n;
+  __device__ __forceinline__ PendingStores(float* dst_) { dst = dst_; n = 0; t0 = 0; }
+  __device__ __forceinline__ void keep(const int o0, const v4f& a0, const bool on = true) {
+    s0 = a0; t0 = o0; n = on ? 1 : 0;
+  }
+  __device__ __forceinline__ void keep_pair(const v4f& a1, const bool on = true) { s1 = a1; n = on ? 2 : 0; }
+  __device__ __forceinline__ void issue() {
+    if (n > 0) *(v4f*)(dst + 16 * t0) = s0;
+    if (n > 1) *(v4f*)(dst + 16 * t0 + 16) = s1;
+    n = 0;
+  }
+};
+
 // Adds the bias to a pair of finished out tiles in front of the product's own hooks: the accumulators then start from
 // zero (no registers until a tile's first matrix instruction) and the pair's two bias tiles fly under its chunk.
 // With all 17 bias tiles loaded before the product -- 68 registers beside the input vector -- the forward kernels of
@@ -116,8 +141,8 @@ struct BiasHooks {
   __device__ __forceinline__ void drain() { inner.drain(); }
 };
 
-// The other order (a core without BIAS_IN_HOOKS): the accumulators start from the bias.  b: the packed bias row, q: the
-// lane's quarter.
+// The other order (a core without BIAS_IN_HOOKS: the two-plane bf16 core): the accumulators start from the bias.
+// b: the packed bias row and the lane's quarter q, or the lane's pointer into the row as BiasHooks takes it and q = 0.
 __device__ __forceinline__ void load_bias(v4f (&acc)[MT], const float* __restrict__ b, const int ot, const int q) {
 #pragma unroll
   for (int t = 0; t < MT; ++t) acc[t] = (t < ot) ? *(const v4f*)(b + 16 * t + 4 * q) : V4ZERO;
@@ -348,6 +373,7 @@ __device__ __forceinline__ void pe_jacobian(v4f (&rbar)[5], const float x0, cons
 // ---------------------------------------------------------------------------
 // The matrix core as the kernel bodies see it (sdf_kernels.h / color_kernels.h are templated on this).
 // gemm(): acc[0..OT) += W * in with the product's hooks (see NoHooks) called per pair of out tiles.
+// gemm_bias(): acc = W * in + bias, the same hooks; `bias` is the lane's pointer into the packed bias row (+ 4 q).
 // ---------------------------------------------------------------------------
 struct CoreF32 {
   typedef v4f wvec;                                  // one 16-byte element of the weight pack
@@ -390,6 +416,29 @@ struct CoreF32 {
   }
 };
 
+// ---------------------------------------------------------------------------
+// What the kernel bodies of both networks share.
+// ---------------------------------------------------------------------------
+// Which point is this lane: lane l of wave w of workgroup wg holds quarter q = l >> 4 of the point at row
+// wg * PTS_PER_WG + 16 w + (l & 15) of the launch grid.  wg: eval_wg() of the SDF kernels (int) or the plain blockIdx.x
+// (unsigned); the product keeps the caller's type, and point and quarter are two calls evaluated where the body needs
+// them: the bf16 kernels' spills moved with either.
+template <class Core, class WG>
+__device__ __forceinline__ int lane_point(const WG wg) {
+  const int lane = lane_id();
+  return wg * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane & 15);
+}
+__device__ __forceinline__ int lane_quarter() { return lane_id() >> 4; }
+
+// The lane's pointer into row `pt` of a tensor or workspace block of rows of `tiles` tiles: block `pre` of a workspace
+// that holds one block per layer, [pre (= the 16 * tiles of the layers before)][P_pad][16 * tiles], or pre = 0 for a
+// plain [P, 16 * tiles] tensor.  This is the layout the weight-gradient kernels and plan.py depend on.
+// t: the lane's pointer to tile t of the row.
+template <class T>
+__device__ __forceinline__ T* lane_row(T* base, const size_t pre, const size_t P_pad, const int pt, const int tiles,
+                                        const int q, const int t = 0) {
+  return base + pre * P_pad + (size_t)pt * (16 * tiles) + 16 * t + 4 * q;
+}
 // ---------------------------------------------------------------------------
 // The fp32 part of a weight pack, the same for every core (third grid plane of the pack kernels, sdf_mlp.hip /
 // sdf_mlp_b16.hip): the layer's bias row in out-slot order and, behind the last layer, the plan's dot-product rows

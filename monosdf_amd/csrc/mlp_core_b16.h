@@ -278,16 +278,22 @@ struct CoreB16N {
     b16_from_tiles<NS>(act, in);
     gemm_b16_dispatch<NS>(kbp, acc, act, OT, wsrc, (v8bf*)lds, hk);
   }
-  // acc = W in + bias (the bias is added to the finished tiles, BiasHooks of mlp_core.h); tiles >= OT leave as zero
+  // acc = W in + bias; tiles >= OT leave as zero.  Three planes: the bias is added to the finished tiles (BiasHooks of
+  // mlp_core.h).  Two planes: the accumulators start from the bias and the plain product follows
   template <class Hooks>
   static __device__ __forceinline__ void gemm_bias(const int kbp, v4f (&acc)[MT], const v4f (&in)[MT], const int OT,
                                                    const wvec* __restrict__ wsrc, void* lds, Hooks&& hk,
                                                    const float* __restrict__ bias) {
-    B16Act<NS> act;
-    b16_from_tiles<NS>(act, in);
-    zero_tiles(acc);
-    BiasHooks<typename std::remove_reference<Hooks>::type> bh(hk, bias, OT);
-    gemm_b16_dispatch<NS>(kbp, acc, act, OT, wsrc, (v8bf*)lds, bh);
+    if constexpr (BIAS_IN_HOOKS) {
+      B16Act<NS> act;
+      b16_from_tiles<NS>(act, in);
+      zero_tiles(acc);
+      BiasHooks<typename std::remove_reference<Hooks>::type> bh(hk, bias, OT);
+      gemm_b16_dispatch<NS>(kbp, acc, act, OT, wsrc, (v8bf*)lds, bh);
+    } else {
+      load_bias(acc, bias, OT, 0);
+      gemm(kbp, acc, in, OT, wsrc, lds, hk);
+    }
   }
 };
 typedef CoreB16N<2> CoreB16;       // "bf16x3"

@@ -33,13 +33,8 @@ __device__ __forceinline__ int eval_wg(const int wg_first = 0) {
   return w;
 }
 
-// The row of the workgroup's grid this lane's point sits at: the EVALUATION row.  Without a row map it is also the row
-// of the point in every tensor.
-template <class Core>
-__device__ __forceinline__ int eval_row(const int wg) {
-  return wg * Core::PTS_PER_WG + (threadIdx.x >> 6) * MLP_PTS_PER_WAVE + (lane_id() & 15);
-}
-
+// The row of workgroup wg's grid that this lane's point sits at (lane_point(), mlp_core.h) is its EVALUATION row.
+// Without a row map it is also the row of the point in every tensor.
 // row_map (cores with ROW_MAP): the point evaluated at row r of the grid is row row_map[r] of the caller's tensors AND
 // of the workspace -- pt / ptc are that row from here on, so nothing below knows about the order of evaluation, and
 // the workspace holds what it holds without a map (the weight-gradient kernels sum its rows in the same order).  An
@@ -49,8 +44,7 @@ __device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, cons
                                                const int32_t* __restrict__ row_map = nullptr,
                                                const int wg = eval_wg<Core>()) {
   PointCtx c;
-  const int lane = lane_id();
-  const int pe = eval_row<Core>(wg);
+  const int pe = lane_point<Core>(wg);
   c.valid = pe < P;
   c.ptc = c.valid ? pe : (P - 1);
   if constexpr (Core::ROW_MAP) {
@@ -60,7 +54,7 @@ __device__ __forceinline__ PointCtx load_point(const float* __restrict__ x, cons
     }
   }
   c.pt = c.valid ? c.ptc : pe;      // the padded tail keeps its own workspace rows
-  c.q = lane >> 4;
+  c.q = lane_quarter();
   c.x0 = x[(size_t)c.ptc * 3 + 0];
   c.x1 = x[(size_t)c.ptc * 3 + 1];
   c.x2 = x[(size_t)c.ptc * 3 + 2];
@@ -179,137 +173,81 @@ __device__ __forceinline__ float sdf_row_dot(const v4f (&in)[MT], const msdf_pla
 }
 
 // ---------------------------------------------------------------------------
-// Product hooks (protocol: mlp_core.h, NoHooks).  Pointers are lane pointers (row of the lane's point + 4 q);
-// tile t of the row sits at p + 16 t.  Results to be stored wait in registers until the next pre() / drain().
+// Product hooks (protocol, lane pointers and the pieces shared below: mlp_core.h, NoHooks).
 // ---------------------------------------------------------------------------
-struct PendingStores {
-  float* dst;
-  v4f s0, s1;
-  int t0, n;
-  __device__ __forceinline__ void issue() {
-    if (n > 0) *(v4f*)(dst + 16 * t0) = s0;
-    if (n > 1) *(v4f*)(dst + 16 * t0 + 16) = s1;
-    n = 0;
-  }
+// Store policies of SoftplusHooks: what becomes of a finished tile besides staying in its accumulator.
+struct NoStores {         // nothing is saved
+  __device__ __forceinline__ NoStores(float* = nullptr) {}
+  __device__ __forceinline__ void keep(const int, const v4f&) {}
+  __device__ __forceinline__ void keep_pair(const v4f&) {}
+  __device__ __forceinline__ void issue() {}
+};
+// PendingStores itself: every lane saves its tiles.
+struct LaneStores : PendingStores {      // decided per lane (no row: a lane whose point is not saved)
+  bool on;
+  __device__ __forceinline__ LaneStores(float* dst_) : PendingStores(dst_), on(dst_ != nullptr) {}
+  __device__ __forceinline__ void issue() { if (on) PendingStores::issue(); else n = 0; }
 };
 
-// h = softplus(a) in place (forward kernel: nothing is saved)
-template <class Core>
+// h = softplus(a) in place on every finished tile.  Stores = NoStores: the forward kernel; PendingStores: h saved to H
+// (forward chain of the fwd+grad kernel); LaneStores: the sampler's forward kernel saving the rows the forward +
+// gradient kernel will reuse.
+template <class Core, class Stores = NoStores>
 struct SoftplusHooks {
-  __device__ __forceinline__ void pre(const int, const int) {}
-  __device__ __forceinline__ void post(const int, const int, const bool pair, v4f& a0, v4f& a1) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) a0[r] = Core::softplus(a0[r]);
-    if (pair) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a1[r] = Core::softplus(a1[r]);
-    }
-  }
-  __device__ __forceinline__ void drain() {}
-};
-
-// h = softplus(a) in place and saved to H (forward chain of the fwd+grad kernel)
-template <class Core>
-struct SoftplusSaveHooks {
-  PendingStores st;
-  __device__ __forceinline__ SoftplusSaveHooks(float* H) { st.dst = H; st.n = 0; st.t0 = 0; }
+  Stores st;
+  __device__ __forceinline__ SoftplusHooks(float* H = nullptr) : st(H) {}
   __device__ __forceinline__ void pre(const int, const int) { st.issue(); }
   __device__ __forceinline__ void post(const int o0, const int, const bool pair, v4f& a0, v4f& a1) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) a0[r] = Core::softplus(a0[r]);
-    st.s0 = a0; st.t0 = o0; st.n = 1;
+    st.keep(o0, a0);
     if (pair) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) a1[r] = Core::softplus(a1[r]);
-      st.s1 = a1; st.n = 2;
+      st.keep_pair(a1);
     }
   }
   __device__ __forceinline__ void drain() { st.issue(); }
 };
 
-// the same with the store decided per lane (on == false: a lane whose point is not saved): the sampler's forward kernel
-// saving the rows the forward + gradient kernel will reuse
-template <class Core>
-struct SoftplusSaveLaneHooks {
-  PendingStores st;
-  bool on;
-  __device__ __forceinline__ SoftplusSaveLaneHooks(float* H) : on(H != nullptr) { st.dst = H; st.n = 0; st.t0 = 0; }
-  __device__ __forceinline__ void pre(const int, const int) { if (on) st.issue(); else st.n = 0; }
-  __device__ __forceinline__ void post(const int o0, const int, const bool pair, v4f& a0, v4f& a1) {
+// g -> s g in place with s = 1 - exp(-100 h): a tile of the gradient sweeps
+__device__ __forceinline__ void scale_by_sigmoid(const v4f& h, v4f& a) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) a0[r] = Core::softplus(a0[r]);
-    st.s0 = a0; st.t0 = o0; st.n = 1;
-    if (pair) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a1[r] = Core::softplus(a1[r]);
-      st.s1 = a1; st.n = 2;
-    }
-  }
-  __device__ __forceinline__ void drain() { if (on) st.issue(); else st.n = 0; }
-};
+  for (int r = 0; r < 4; ++r) a[r] = (1.0f - one_minus_sigmoid_from_h(h[r])) * a[r];
+}
 
-// gradient sweep of the fwd+grad kernel: g -> p = s g with s = 1 - exp(-100 h), h loaded from H; p saved to PM.
+// gradient sweep of the fwd+grad kernel: g -> p = s g, h loaded from Hsrc; p saved to PM.
 // Tiles >= ot (the input block behind a skip layer's hidden tiles; ot == 0: no epilogue at all) are left alone.
+// COPY: a workgroup that reuses the hidden activations the sampler's forward kernel staged (rows in evaluation
+// order): Hsrc is the staged row and h is stored to the point's own row of H on the way -- the loads replace the
+// sweep's own loads of H, the stores are the ones the forward chain would have issued.  Otherwise Hsrc is that row of
+// H.
+template <bool COPY>
 struct GradSweepHooks {
-  const float* H;
+  const float* Hsrc;
+  float* H;             // written under COPY only (otherwise unused: no register)
   int ot;
   bool save;
   v4f h0, h1;
   PendingStores st;
-  __device__ __forceinline__ GradSweepHooks(const float* H_, float* PM, const int ot_, const bool save_)
-      : H(H_), ot(ot_), save(save_) { st.dst = PM; st.n = 0; st.t0 = 0; }
+  __device__ __forceinline__ GradSweepHooks(const float* Hsrc_, float* H_, float* PM, const int ot_, const bool save_)
+      : Hsrc(Hsrc_), H(H_), ot(ot_), save(save_), st(PM) {}
   __device__ __forceinline__ void pre(const int o0, const int o1) {
     st.issue();
     if (ot > 0) {
-      h0 = *(const v4f*)(H + 16 * (o0 < ot ? o0 : ot - 1));
-      h1 = *(const v4f*)(H + 16 * (o1 < ot ? o1 : ot - 1));
+      h0 = *(const v4f*)(Hsrc + 16 * (o0 < ot ? o0 : ot - 1));
+      h1 = *(const v4f*)(Hsrc + 16 * (o1 < ot ? o1 : ot - 1));
     }
   }
   __device__ __forceinline__ void post(const int o0, const int o1, const bool pair, v4f& a0, v4f& a1) {
     if (o0 < ot) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a0[r] = (1.0f - one_minus_sigmoid_from_h(h0[r])) * a0[r];
-      st.s0 = a0; st.t0 = o0; st.n = save ? 1 : 0;
+      if constexpr (COPY) *(v4f*)(H + 16 * o0) = h0;
+      scale_by_sigmoid(h0, a0);
+      st.keep(o0, a0, save);
       if (pair && o1 < ot) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a1[r] = (1.0f - one_minus_sigmoid_from_h(h1[r])) * a1[r];
-        st.s1 = a1; st.n = save ? 2 : 0;
-      }
-    }
-  }
-  __device__ __forceinline__ void drain() { st.issue(); }
-};
-
-// The same for a workgroup that reuses the hidden activations the sampler's forward kernel staged (HS, rows in
-// evaluation order): h comes from the staged row and is stored to the point's own row of H on the way -- the loads
-// replace the sweep's own loads of H, the stores are the ones the forward chain would have issued.
-struct GradSweepCopyHooks {
-  const float* HS;
-  float* H;
-  int ot;
-  bool save;
-  v4f h0, h1;
-  PendingStores st;
-  __device__ __forceinline__ GradSweepCopyHooks(const float* HS_, float* H_, float* PM, const int ot_, const bool save_)
-      : HS(HS_), H(H_), ot(ot_), save(save_) { st.dst = PM; st.n = 0; st.t0 = 0; }
-  __device__ __forceinline__ void pre(const int o0, const int o1) {
-    st.issue();
-    if (ot > 0) {
-      h0 = *(const v4f*)(HS + 16 * (o0 < ot ? o0 : ot - 1));
-      h1 = *(const v4f*)(HS + 16 * (o1 < ot ? o1 : ot - 1));
-    }
-  }
-  __device__ __forceinline__ void post(const int o0, const int o1, const bool pair, v4f& a0, v4f& a1) {
-    if (o0 < ot) {
-      *(v4f*)(H + 16 * o0) = h0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a0[r] = (1.0f - one_minus_sigmoid_from_h(h0[r])) * a0[r];
-      st.s0 = a0; st.t0 = o0; st.n = save ? 1 : 0;
-      if (pair && o1 < ot) {
-        *(v4f*)(H + 16 * o1) = h1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a1[r] = (1.0f - one_minus_sigmoid_from_h(h1[r])) * a1[r];
-        st.s1 = a1; st.n = save ? 2 : 0;
+        if constexpr (COPY) *(v4f*)(H + 16 * o1) = h1;
+        scale_by_sigmoid(h1, a1);
+        st.keep_pair(a1, save);
       }
     }
   }
@@ -330,12 +268,8 @@ struct SweepUpHooks {
     h1 = *(const v4f*)(H + 16 * c1);
   }
   __device__ __forceinline__ void post(const int, const int, const bool pair, v4f& a0, v4f& a1) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) a0[r] = (1.0f - one_minus_sigmoid_from_h(h0[r])) * a0[r];
-    if (pair) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a1[r] = (1.0f - one_minus_sigmoid_from_h(h1[r])) * a1[r];
-    }
+    scale_by_sigmoid(h0, a0);
+    if (pair) scale_by_sigmoid(h1, a1);
   }
   __device__ __forceinline__ void drain() {}
 };
@@ -351,7 +285,7 @@ struct SweepDownHooks {
   v4f h0, h1, p0, p1, q0, q1;
   PendingStores st;
   __device__ __forceinline__ SweepDownHooks(const float* H_, const float* PM_, const float* Q_, float* AB, const int ot_)
-      : H(H_), PM(PM_), Q(Q_), ot(ot_) { st.dst = AB; st.n = 0; st.t0 = 0; }
+      : H(H_), PM(PM_), Q(Q_), ot(ot_), st(AB) {}
   __device__ __forceinline__ void pre(const int o0, const int o1) {
     st.issue();
     if (ot > 0) {
@@ -376,10 +310,10 @@ struct SweepDownHooks {
   __device__ __forceinline__ void post(const int o0, const int o1, const bool pair, v4f& a0, v4f& a1) {
     if (o0 < ot) {
       tile(h0, p0, q0, a0);
-      st.s0 = a0; st.t0 = o0; st.n = 1;
+      st.keep(o0, a0);
       if (pair && o1 < ot) {
         tile(h1, p1, q1, a1);
-        st.s1 = a1; st.n = 2;
+        st.keep_pair(a1);
       }
     }
   }
@@ -428,17 +362,14 @@ __device__ __forceinline__ void sdf_forward_body(const msdf_plan_t& plan, const 
       load_input_tiles<Core::AUX_LEVEL_MAJOR>(in0, plan, aux, av, c);
       place_tiles(in, L.skip_tile, in0, in0_tiles);
     }
+    static_assert(!SAVE || Core::BIAS_IN_HOOKS, "the save kernel exists for the fp32 core");
+    typedef typename std::conditional<SAVE, LaneStores, NoStores>::type Stores;
+    float* Hl = nullptr;
     if constexpr (SAVE) {
-      static_assert(!SAVE || Core::BIAS_IN_HOOKS, "the save kernel exists for the fp32 core");
-      float* Hl = (srow >= 0) ? hs.H + (size_t)L.hpre * hs.P_pad + (size_t)srow * (16 * L.ot) + 4 * c.q : nullptr;
-      Core::gemm_bias(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusSaveLaneHooks<Core>(Hl),
-                      bpack + L.bias_off + 4 * c.q);
-    } else if constexpr (Core::BIAS_IN_HOOKS) {
-      Core::gemm_bias(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusHooks<Core>(), bpack + L.bias_off + 4 * c.q);
-    } else {
-      load_bias(acc, bpack + L.bias_off, L.ot, c.q);
-      Core::gemm(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusHooks<Core>());
+      if (srow >= 0) Hl = lane_row(hs.H, L.hpre, hs.P_pad, srow, L.ot, c.q);
     }
+    Core::gemm_bias(L.ktp, acc, in, L.ot, wpack + L.wf_off, lds, SoftplusHooks<Core, Stores>(Hl),
+                    bpack + L.bias_off + 4 * c.q);
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = (t < L.ot) ? acc[t] : V4ZERO;
   }
@@ -488,15 +419,17 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     if (a.save) {
 #pragma unroll
       for (int t = 0; t < 5; ++t)
-        if (t < in0_tiles) *(v4f*)(a.IN0 + (size_t)c.pt * (16 * in0_tiles) + 16 * t + 4 * c.q) = in0[t];
+        if (t < in0_tiles) *(v4f*)lane_row(a.IN0, 0, 0, c.pt, in0_tiles, c.q, t) = in0[t];
     }
   }
   // workgroup-uniform on purpose: the gemm below contains barriers and cooperative weight staging
   const bool want_feat = wg * Core::PTS_PER_WG < a.n_feat;
 
-  // the point's staged row of layer L (REUSE): evaluation order, stage_pad rows per layer block
+  // the point's staged row of layer L (REUSE): evaluation order, stage_pad rows per layer block.  lane_row()'s
+  // arithmetic as an offset, spelled here: through a helper the sum's order and flags change and the bf16 kernels
+  // spill more
   auto srow = [&](const msdf_layer_t& L) {
-    return (size_t)L.hpre * (size_t)a.stage_pad + (size_t)eval_row<Core>(wg) * (16 * L.ot) + 4 * c.q;
+    return (size_t)L.hpre * (size_t)a.stage_pad + (size_t)lane_point<Core>(wg) * (16 * L.ot) + 4 * c.q;
   };
   // ---------------- forward chain ----------------
   if constexpr (REUSE) {
@@ -517,13 +450,15 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
       load_input_tiles<Core::AUX_LEVEL_MAJOR>(in0, plan, a.aux, av, c);
       place_tiles(in, L.skip_tile, in0, in0_tiles);
     }
-    float* Hl = a.H + (size_t)L.hpre * Pp + (size_t)c.pt * (16 * L.ot) + 4 * c.q;
+    float* Hl = lane_row(a.H, L.hpre, Pp, c.pt, L.ot, c.q);
+    // the two-plane bf16 core's biased product written out (as in CoreB16N<2>::gemm_bias): through the call this
+    // kernel of that core spills two more registers
     if constexpr (Core::BIAS_IN_HOOKS) {
-      Core::gemm_bias(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, SoftplusSaveHooks<Core>(Hl),
-                      a.bpack + L.bias_off + 4 * c.q);
+      Core::gemm_bias(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds,
+                      SoftplusHooks<Core, PendingStores>(Hl), a.bpack + L.bias_off + 4 * c.q);
     } else {
       load_bias(acc, a.bpack + L.bias_off, L.ot, c.q);
-      Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, SoftplusSaveHooks<Core>(Hl));
+      Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, SoftplusHooks<Core, PendingStores>(Hl));
     }
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = (t < L.ot) ? acc[t] : V4ZERO;
@@ -540,7 +475,7 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
       Core::gemm(LL.ktp, acc, in, LL.ot, (const wvec*)a.wpack + LL.wf_off, lds, NoHooks());
     }
     if (c.valid && c.pt < a.n_feat) {
-      float* f = a.feat + (size_t)c.pt * (16 * plan.feat_tiles) + 4 * c.q;
+      float* f = lane_row(a.feat, 0, 0, c.pt, plan.feat_tiles, c.q);
 #pragma unroll
       for (int t = 0; t < MT; ++t)
         if (t < plan.feat_tiles) *(v4f*)(f + 16 * t) = acc[t];
@@ -575,6 +510,8 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     r_aux[0] += r[3];
     r_aux[1] += r[4];
   };
+  // the point's row of layer L in H and in PM, which hold a layer's rows alike: lane_row()'s arithmetic as one offset
+  // for both, spelled here for the same reason as srow
   auto row = [&](const msdf_layer_t& L) { return (size_t)L.hpre * Pp + (size_t)c.pt * (16 * L.ot) + 4 * c.q; };
   if (nl >= 2) {
     // p of the last hidden layer: no product precedes it (g is the sdf row itself) -- every H load before
@@ -590,8 +527,7 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     for (int t = 0; t < MT; ++t) {
       if (t == 0 || t < L.ot) {
         if constexpr (REUSE) *(v4f*)(a.H + row(L) + 16 * t) = hh[t];      // the staged row becomes the point's row of H
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[t][r] = (1.0f - one_minus_sigmoid_from_h(hh[t][r])) * acc[t][r];
+        scale_by_sigmoid(hh[t], acc[t]);
         if (a.save) *(v4f*)(Pl + 16 * t) = acc[t];
       }
     }
@@ -604,13 +540,9 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     for (int t = 0; t < MT; ++t) in[t] = (t < L.ot) ? acc[t] : V4ZERO;
     zero_tiles(acc);
     const msdf_layer_t Lp = plan.layer[l > 0 ? l - 1 : 0];
-    if constexpr (REUSE) {
-      Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
-                 GradSweepCopyHooks(a.h_stage + srow(Lp), a.H + row(Lp), a.PM + row(Lp), l > 0 ? Lp.ot : 0, a.save != 0));
-    } else {
-      Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
-                 GradSweepHooks(a.H + row(Lp), a.PM + row(Lp), l > 0 ? Lp.ot : 0, a.save != 0));
-    }
+    Core::gemm(L.otp, acc, in, L.kt, (const wvec*)a.wpack + L.wb_off, lds,
+               GradSweepHooks<REUSE>(REUSE ? a.h_stage + srow(Lp) : a.H + row(Lp), a.H + row(Lp), a.PM + row(Lp),
+                                     l > 0 ? Lp.ot : 0, a.save != 0));
     if (l == 0) take_input_grad(0);
     else if (L.skip_tile >= 0) take_input_grad(L.skip_tile);
   }
@@ -737,22 +669,22 @@ __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const
       load_rbar<Core::AUX_LEVEL_MAJOR>(rbar, plan, a, c, live, gn0, gn1, gn2);
       place_tiles(in, L.skip_tile, rbar, in0_tiles);
     }
-    float* Ql = a.QB + (size_t)L.qpre * Pp + (size_t)c.pt * (16 * L.kt) + 4 * c.q;
+    float* Ql = lane_row(a.QB, L.qpre, Pp, c.pt, L.kt, c.q);
 #pragma unroll
     for (int t = 0; t < MT; ++t)
       if (t < L.kt) *(v4f*)(Ql + 16 * t) = in[t];
     zero_tiles(acc);
-    const size_t off = (size_t)L.hpre * Pp + (size_t)c.pt * (16 * L.ot) + 4 * c.q;
+    const float* Hl = lane_row(a.H, L.hpre, Pp, c.pt, L.ot, c.q);
     // the hooks turn p-bar into q-bar of the next layer chunk by chunk, loading H / PM and storing T under the
     // product's own matrix instructions
-    Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, SweepUpHooks(a.H + off, L.ot));
+    Core::gemm(L.ktp, acc, in, L.ot, (const wvec*)a.wpack + L.wf_off, lds, SweepUpHooks(Hl, L.ot));
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = (t < L.ot) ? acc[t] : V4ZERO;
   }
   const msdf_layer_t LL = plan.layer[nl - 1];
   {
     // q-bar of the last layer's input: d W_last[sdf row] = sum_p q-bar (one row of ones on the X side)
-    float* Ql = a.QLAST + (size_t)c.pt * (16 * LL.kt) + 4 * c.q;
+    float* Ql = lane_row(a.QLAST, 0, 0, c.pt, LL.kt, c.q);
 #pragma unroll
     for (int t = 0; t < MT; ++t)
       if (t < LL.kt) *(v4f*)(Ql + 16 * t) = in[t];
@@ -762,7 +694,7 @@ __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const
   // a-bar of the output layer: feature gradient tiles + the sdf slot
   const bool has_feat = (a.g_feat != nullptr) && c.valid && c.pt < a.n_feat;
   {
-    float* ABl = a.AB + (size_t)LL.abpre * Pp + (size_t)c.pt * (16 * LL.ot) + 4 * c.q;
+    float* ABl = lane_row(a.AB, LL.abpre, Pp, c.pt, LL.ot, c.q);
     // every load before the first store (as in the hooks: a store next to each load is one memory round trip per tile)
     const float* gf = a.g_feat + (size_t)(has_feat ? c.pt : 0) * (16 * plan.feat_tiles) + 4 * c.q;
     const int ftl = plan.feat_tiles - 1;
@@ -783,14 +715,15 @@ __device__ __forceinline__ void sdf_backward_body(const msdf_plan_t& plan, const
   // (H / T loaded, AB stored under the product's matrix instructions)
   auto down_hooks = [&](const int l) {     // hooks of the product whose output feeds layer l (l < 0: none)
     const msdf_layer_t Ln = plan.layer[l >= 0 ? l : 0];
+    // H and PM rows alike: lane_row()'s arithmetic as one offset, spelled here (as a helper call the sum is ordered
+    // differently and the bf16x3 backward kernel takes 8 bytes more scratch)
     const size_t off = (size_t)Ln.hpre * Pp + (size_t)c.pt * (16 * Ln.ot) + 4 * c.q;
     // q-bar of layer l's outputs = the input rows stored for layer l + 1 (QLAST above the last hidden layer)
     const int ln = (l >= 0 ? l : 0) + 1;
     const msdf_layer_t Lq = plan.layer[ln];
-    const float* Q = (ln == nl - 1) ? a.QLAST + (size_t)c.pt * (16 * Lq.kt) + 4 * c.q
-                                    : a.QB + (size_t)Lq.qpre * Pp + (size_t)c.pt * (16 * Lq.kt) + 4 * c.q;
-    return SweepDownHooks(a.H + off, a.PM + off, Q,
-                          a.AB + (size_t)Ln.abpre * Pp + (size_t)c.pt * (16 * Ln.ot) + 4 * c.q, l >= 0 ? Ln.ot : 0);
+    const float* Q = (ln == nl - 1) ? lane_row(a.QLAST, 0, 0, c.pt, Lq.kt, c.q)
+                                    : lane_row(a.QB, Lq.qpre, Pp, c.pt, Lq.kt, c.q);
+    return SweepDownHooks(a.H + off, a.PM + off, Q, lane_row(a.AB, Ln.abpre, Pp, c.pt, Ln.ot, c.q), l >= 0 ? Ln.ot : 0);
   };
   Core::gemm(LL.otp, acc, in, LL.kt, (const wvec*)a.wpack + LL.wb_off, lds, down_hooks(nl - 2));
   v4f g_in_aux[5];      // only the aux tiles (hash-grid features) of d loss / d input are an output
