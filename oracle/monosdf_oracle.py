@@ -162,7 +162,8 @@ def color_network(state, conf, points, normals, view_dirs, feats, indices=None,
 def transmittance_weights(z_vals, density):
     """alpha_i * T_i with an exclusive prefix sum of free energy (network.py:626-640)."""
     dists = z_vals[:, 1:] - z_vals[:, :-1]
-    dists = torch.cat([dists, torch.full_like(dists[:, :1], 1e10)], -1)
+    # one 1e10 per RAY, like the reference's repeat(dists.shape[0], 1): with one sample `dists` has no column to copy
+    dists = torch.cat([dists, torch.full_like(z_vals[:, :1], 1e10)], -1)
     free = dists * density
     shifted = torch.cat([torch.zeros_like(free[:, :1]), free[:, :-1]], -1)
     alpha = 1 - torch.exp(-free)
