@@ -47,8 +47,10 @@ __device__ __forceinline__ float smp_density(const float s, const float beta) {
   const float sg = (s > 0.f) ? 1.f : (s < 0.f) ? -1.f : 0.f;
   return (1.0f / beta) * (0.5f + 0.5f * sg * e);
 }
-// torch.linspace(0, 1, n)[j] (symmetric evaluation, like ATen's kernel)
+// torch.linspace(0, 1, n)[j] (symmetric evaluation, like ATen's kernel); one step is the start alone, as in ATen
+// (the step 1 / (n - 1) below would be infinite, and 1 - inf * 0 a NaN sample)
 __device__ __forceinline__ float smp_linspace01(const int j, const int n) {
+  if (n < 2) return 0.0f;
   const float step = 1.0f / (float)(n - 1);
   return (j < n / 2) ? step * (float)j : 1.0f - step * (float)(n - 1 - j);
 }

@@ -104,6 +104,12 @@ def _set(section, **kw):
     return edit
 
 
+def _no_weight_norm(conf):
+    # plain Linear layers in both networks: the weight-norm kernels' pass-through rows, forward and backward
+    conf['implicit_network']['weight_norm'] = False
+    conf['rendering_network']['weight_norm'] = False
+
+
 VARIANTS = {
     'no_positional_encoding': _set('implicit_network', multires=0),
     'multires_4': _set('implicit_network', multires=4),
@@ -114,6 +120,7 @@ VARIANTS = {
     'view_pe_2': _set('rendering_network', multires_view=2),
     'colour_3_hidden': _set('rendering_network', dims=[64, 64, 64]),
     'colour_1_hidden': _set('rendering_network', dims=[64]),
+    'no_weight_norm': _no_weight_norm,
 }
 
 
