@@ -14,6 +14,69 @@ static inline int msdf_check_launch() {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// Wave primitives of the ray-pipeline kernels and the mesh tools.  The order of the shuffle offsets is the summation
+// order, which the results depend on bit for bit.  No fp-contract pragma here: each translation unit compiles these
+// with its own flags (csrc/Makefile).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// exclusive prefix sum, by scanning the values shifted up one lane.  (inclusive - self would cancel catastrophically
+// against the 1e10 * sigma free energy of the last interval)
+__device__ __forceinline__ float wave_excl_scan(const float v) {
+  float prev = __shfl_up(v, 1, 64);
+  if (lane_id() == 0) prev = 0.f;
+  return wave_incl_scan(prev);
+}
+// the same; `total` = sum over the wave
+__device__ __forceinline__ float wave_excl_scan(const float v, float& total) {
+  const float ex = wave_excl_scan(v);
+  total = __shfl(ex, 63, 64) + __shfl(v, 63, 64);
+  return ex;
+}
+
+// exclusive suffix sum: sum of v over lanes > lane; `total` = sum over the wave.  Built from a shifted
+// reverse scan so that a lane with nothing after it gets EXACTLY 0 (total - inclusive would leave
+// rounding noise, which the 1e10 last-interval length then multiplies into the sdf / beta gradients).
+__device__ __forceinline__ float wave_excl_suffix(const float v, float& total) {
+  const int lane = lane_id();
+  float s = __shfl_down(v, 1, 64);
+  if (lane == 63) s = 0.f;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float o = __shfl_down(s, d, 64);
+    if (lane + d < 64) s += o;
+  }
+  total = __shfl(s, 0, 64) + __shfl(v, 0, 64);
+  return s;
+}
+
+__device__ __forceinline__ float sgnf(const float v) { return (v > 0.f) ? 1.f : (v < 0.f) ? -1.f : 0.f; }
+
+// LaplaceDensity.density_func (code/model/density.py:21-30): sigma(s) = (1/beta) (0.5 + 0.5 sign(s) expm1(-|s|/beta))
+__device__ __forceinline__ float laplace_density(const float s, const float beta) {
+  const float e = expm1f(-fabsf(s) / beta);
+  return (1.0f / beta) * (0.5f + 0.5f * sgnf(s) * e);
+}
+
 // exp / log on the hardware transcendental unit (v_exp_f32 / v_log_f32, ~1 ulp)
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float fast_log(float x) { return __logf(x); }

@@ -9,39 +9,6 @@
 
 #define CMP_MAX_PER_LANE 4      // supports up to 256 samples per ray
 
-__device__ __forceinline__ float wave_incl_scan(float v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive prefix sum; `total` = sum over the wave.  (inclusive - self would cancel catastrophically
-// against the 1e10 * sigma free energy of the last interval)
-__device__ __forceinline__ float wave_excl_scan(const float v, float& total) {
-  float prev = __shfl_up(v, 1, 64);
-  if (lane_id() == 0) prev = 0.f;
-  const float ex = wave_incl_scan(prev);
-  total = __shfl(ex, 63, 64) + __shfl(v, 63, 64);
-  return ex;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// sigma(s) = (1/beta) (0.5 + 0.5 sign(s) expm1(-|s|/beta))
-__device__ __forceinline__ float laplace_density(const float s, const float beta) {
-  const float e = expm1f(-fabsf(s) / beta);
-  const float sg = (s > 0.f) ? 1.f : (s < 0.f) ? -1.f : 0.f;
-  return (1.0f / beta) * (0.5f + 0.5f * sg * e);
-}
-
 typedef msdf_composite_args_t CompositeArgs;
 
 __global__ void __launch_bounds__(256)
@@ -111,22 +78,6 @@ msdf_composite_forward_k(const CompositeArgs a) {
 }
 
 typedef msdf_composite_bwd_args_t CompositeBwdArgs;
-
-// exclusive suffix sum: sum of v over lanes > lane; `total` = sum over the wave.  Built from a shifted
-// reverse scan so that a lane with nothing after it gets EXACTLY 0 (total - inclusive would leave
-// rounding noise, which the 1e10 last-interval length then multiplies into the sdf / beta gradients).
-__device__ __forceinline__ float wave_excl_suffix(const float v, float& total) {
-  const int lane = lane_id();
-  float s = __shfl_down(v, 1, 64);
-  if (lane == 63) s = 0.f;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = __shfl_down(s, d, 64);
-    if (lane + d < 64) s += o;
-  }
-  total = __shfl(s, 0, 64) + __shfl(v, 0, 64);
-  return s;
-}
 
 __global__ void __launch_bounds__(256)
 msdf_composite_backward_k(const CompositeBwdArgs a) {
@@ -249,7 +200,7 @@ msdf_beta_grad_k(const float* __restrict__ raw, const float* __restrict__ part, 
   for (int i = threadIdx.x; i < n; i += 64) s += part[i];
   s = wave_sum(s);
   const float r = raw[0];
-  if (threadIdx.x == 0) g_raw[0] = ((r > 0.f) ? 1.f : (r < 0.f) ? -1.f : 0.f) * s;
+  if (threadIdx.x == 0) g_raw[0] = sgnf(r) * s;
 }
 extern "C" int msdf_beta_eff(const float* beta_raw, float beta_min, float* out, void* stream) {
   if (beta_raw == nullptr || out == nullptr) return MSDF_ERR_ARG;

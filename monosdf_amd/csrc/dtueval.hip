@@ -206,8 +206,7 @@ dt_lattice_count_k(const float* __restrict__ verts, int64_t n_verts, const int32
   const LatFace L = lat_face(verts, n_verts, faces, f, density);
   long long sum = 0;
   for (int64_t i = lane; i < L.rows; i += MSDF_WAVE) sum += lat_row(L, i);
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s, MSDF_WAVE);
+  sum = wave_sum(sum);
   if (lane == 0) counts[f] = L.too_many ? LAT_TOO_MANY : (int64_t)sum;
 }
 
@@ -224,12 +223,7 @@ dt_lattice_emit_k(const float* __restrict__ verts, int64_t n_verts, const int32_
   int64_t done = 0;
   for (int64_t i0 = 0; i0 < L.rows; i0 += MSDF_WAVE) {                  // every lane runs every shuffle below
     const long long c = lat_row(L, i0 + lane);
-    long long incl = c;
-#pragma unroll
-    for (int s = 1; s < MSDF_WAVE; s <<= 1) {
-      const long long up = __shfl_up(incl, s, MSDF_WAVE);
-      if (lane >= s) incl += up;
-    }
+    const long long incl = wave_incl_scan(c);
     const long long total = __shfl(incl, MSDF_WAVE - 1, MSDF_WAVE);
     for (long long pb = 0; pb < total; pb += MSDF_WAVE) {
       const long long p = pb + lane;

@@ -6,16 +6,62 @@
 // msdf_monosdf_loss below is the reference's training loss.
 #include "common.h"
 
-__device__ __forceinline__ float sgnf(const float v) { return (v > 0.f) ? 1.f : (v < 0.f) ? -1.f : 0.f; }
+#define ML_THREADS 1024
+
+// sums[k] over the whole workgroup, result broadcast to every thread through `red`
+template <int K>
+__device__ __forceinline__ void ml_block_sum(float (&v)[K], float* red) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();                                   // previous users of `red` are done
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float s = 0.f;
+    for (int w = 0; w < ML_THREADS / 64; ++w) s += red[w * K + k];
+    v[k] = s;
+  }
+}
+
+// One row of the eikonal term (|g1| - 1)^2 and the smoothness term |n1 - n2|, n = g / (|g| + 1e-5), both taken as
+// means with factor `mean`.  Writes the row's gradients, gives back e = |g1| - 1 and s = |n1 - n2|; the caller adds
+// its own function of them to its own sums.
+__device__ __forceinline__ void eik_smooth_row(const float* g1, const float* g2, const float w_eik, const float w_smooth,
+                                               const float mean, float* g_g1, float* g_g2, float& e, float& s) {
+  const float l1 = sqrtf(g1[0] * g1[0] + g1[1] * g1[1] + g1[2] * g1[2]);
+  const float l2 = sqrtf(g2[0] * g2[0] + g2[1] * g2[1] + g2[2] * g2[2]);
+  e = l1 - 1.0f;
+  const float d1 = l1 + 1e-5f, d2 = l2 + 1e-5f;
+  float d[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) d[c] = g1[c] / d1 - g2[c] / d2;
+  s = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  // u = d / s (0 at s == 0); d loss/d n1 = +k u, d loss/d n2 = -k u; n = g/(|g|+eps)
+  const float k = (s > 0.f) ? w_smooth * mean / s : 0.f;
+  const float ug1 = d[0] * g1[0] + d[1] * g1[1] + d[2] * g1[2];
+  const float ug2 = d[0] * g2[0] + d[1] * g2[1] + d[2] * g2[2];
+  const float eik = (l1 > 0.f) ? w_eik * 2.0f * e * mean / l1 : 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float j1 = d[c] / d1 - ((l1 > 0.f) ? g1[c] * ug1 / (l1 * d1 * d1) : 0.f);
+    const float j2 = d[c] / d2 - ((l2 > 0.f) ? g2[c] * ug2 / (l2 * d2 * d2) : 0.f);
+    g_g1[c] = eik * g1[c] + k * j1;
+    g_g2[c] = -k * j2;
+  }
+}
 
 // ONE workgroup of 1,024 threads (the batch is ~1k rays and 2k eikonal points): the loss value leaves the kernel
 // complete -- thread-serial partial sums, wave butterflies, the 16 wave sums added in order -- so that no reduction
 // launch follows it.
-__global__ void __launch_bounds__(1024)
+__global__ void __launch_bounds__(ML_THREADS)
 msdf_probe_loss_k(const msdf_probe_loss_args_t a) {
   float part = 0.f;
   const int n_rows = a.N > a.M ? a.N : a.M;
-  for (int i = threadIdx.x; i < n_rows; i += 1024) {
+  for (int i = threadIdx.x; i < n_rows; i += ML_THREADS) {
   if (i < a.N) {
     const float inv3n = 1.0f / (3.0f * a.N);
 #pragma unroll
@@ -32,44 +78,18 @@ msdf_probe_loss_k(const msdf_probe_loss_args_t a) {
   }
   if (i < a.M) {
     const float invm = 1.0f / a.M;
-    const float* g1 = a.g1 + (size_t)i * 3;
-    const float* g2 = a.g2 + (size_t)i * 3;
-    const float l1 = sqrtf(g1[0] * g1[0] + g1[1] * g1[1] + g1[2] * g1[2]);
-    const float l2 = sqrtf(g2[0] * g2[0] + g2[1] * g2[1] + g2[2] * g2[2]);
-    const float e = l1 - 1.0f;
+    float e, sn;
+    eik_smooth_row(a.g1 + (size_t)i * 3, a.g2 + (size_t)i * 3, a.w_eik, a.w_smooth, invm, a.g_g1 + (size_t)i * 3,
+                   a.g_g2 + (size_t)i * 3, e, sn);
     part += a.w_eik * e * e * invm;
-    const float d1 = l1 + 1e-5f, d2 = l2 + 1e-5f;
-    float n1[3], n2[3], d[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { n1[c] = g1[c] / d1; n2[c] = g2[c] / d2; d[c] = n1[c] - n2[c]; }
-    const float s = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    part += a.w_smooth * s * invm;
-    // u = d / s (0 at s == 0); d loss/d n1 = +k u, d loss/d n2 = -k u; n = g/(|g|+eps)
-    const float k = (s > 0.f) ? a.w_smooth * invm / s : 0.f;
-    const float ug1 = (d[0] * g1[0] + d[1] * g1[1] + d[2] * g1[2]);
-    const float ug2 = (d[0] * g2[0] + d[1] * g2[1] + d[2] * g2[2]);
-    const float eik = (l1 > 0.f) ? a.w_eik * 2.0f * e * invm / l1 : 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float j1 = d[c] / d1 - ((l1 > 0.f) ? g1[c] * ug1 / (l1 * d1 * d1) : 0.f);
-      const float j2 = d[c] / d2 - ((l2 > 0.f) ? g2[c] * ug2 / (l2 * d2 * d2) : 0.f);
-      a.g_g1[(size_t)i * 3 + c] = eik * g1[c] + k * j1;
-      a.g_g2[(size_t)i * 3 + c] = -k * j2;
-    }
+    part += a.w_smooth * sn * invm;
   }
   }
   // reduction of the loss value over the workgroup, fixed order
-  __shared__ float red[16];
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) part += __shfl_xor(part, dlt, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += red[w];
-    a.partial[0] = t;
-  }
+  __shared__ float red[ML_THREADS / 64];
+  float loss[1] = {part};
+  ml_block_sum<1>(loss, red);
+  if (threadIdx.x == 0) a.partial[0] = loss[0];
 }
 
 // ---------------------------------------------------------------------------
@@ -86,7 +106,6 @@ msdf_probe_loss_k(const msdf_probe_loss_args_t a) {
 // squared residual), so the gradient is m * res * scale / M; the fixtures recorded from the reference's
 // autograd confirm it to rounding.  All reductions are fixed-order (thread-serial, wave butterfly, 16 waves).
 // ---------------------------------------------------------------------------
-#define ML_THREADS 1024
 #define ML_NSUM 10
 
 __device__ __forceinline__ float ml_gamma2(const float x) {
@@ -94,27 +113,6 @@ __device__ __forceinline__ float ml_gamma2(const float x) {
 }
 __device__ __forceinline__ float ml_gamma2_grad(const float x) {
   return (x <= 0.0031308f) ? 12.92f : (1.055f / 2.4f) * __powf(x, 1.0f / 2.4f - 1.0f);
-}
-
-// sums[k] over the whole workgroup, result broadcast to every thread through `red`
-template <int K>
-__device__ __forceinline__ void ml_block_sum(float (&v)[K], float* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();                                   // previous users of `red` are done
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = 0.f;
-    for (int w = 0; w < ML_THREADS / 64; ++w) s += red[w * K + k];
-    v[k] = s;
-  }
 }
 
 __global__ void __launch_bounds__(ML_THREADS)
@@ -179,29 +177,11 @@ msdf_monosdf_loss_k(const msdf_monosdf_loss_args_t a) {
   if (a.grad_theta != nullptr) {
     const float inve = 1.0f / E;
     for (int i = tid; i < E; i += ML_THREADS) {
-      const float* g1 = a.grad_theta + (size_t)i * 3;
-      const float* g2 = a.grad_nei + (size_t)i * 3;
-      const float l1 = sqrtf(g1[0] * g1[0] + g1[1] * g1[1] + g1[2] * g1[2]);
-      const float l2 = sqrtf(g2[0] * g2[0] + g2[1] * g2[1] + g2[2] * g2[2]);
-      const float e = l1 - 1.0f;
+      float e, sn;
+      eik_smooth_row(a.grad_theta + (size_t)i * 3, a.grad_nei + (size_t)i * 3, a.w_eik, a.w_smooth, inve,
+                     a.g_theta + (size_t)i * 3, a.g_nei + (size_t)i * 3, e, sn);
       sums[8] += e * e;
-      const float d1 = l1 + 1e-5f, d2 = l2 + 1e-5f;
-      float d[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d[c] = g1[c] / d1 - g2[c] / d2;
-      const float sn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
       sums[9] += sn;
-      const float k = (sn > 0.f) ? a.w_smooth * inve / sn : 0.f;
-      const float ug1 = d[0] * g1[0] + d[1] * g1[1] + d[2] * g1[2];
-      const float ug2 = d[0] * g2[0] + d[1] * g2[1] + d[2] * g2[2];
-      const float eik = (l1 > 0.f) ? a.w_eik * 2.0f * e * inve / l1 : 0.f;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float j1 = d[c] / d1 - ((l1 > 0.f) ? g1[c] * ug1 / (l1 * d1 * d1) : 0.f);
-        const float j2 = d[c] / d2 - ((l2 > 0.f) ? g2[c] * ug2 / (l2 * d2 * d2) : 0.f);
-        a.g_theta[(size_t)i * 3 + c] = eik * g1[c] + k * j1;
-        a.g_nei[(size_t)i * 3 + c] = -k * j2;
-      }
     }
   }
   ml_block_sum<ML_NSUM>(sums, red);
@@ -243,6 +223,6 @@ extern "C" int msdf_monosdf_loss(const msdf_monosdf_loss_args_t* a, void* stream
 
 extern "C" int msdf_probe_loss(const msdf_probe_loss_args_t* a, void* stream) {
   if (a == nullptr || a->N < 1 || a->M < 0) return MSDF_ERR_ARG;
-  msdf_probe_loss_k<<<1, 1024, 0, (hipStream_t)stream>>>(*a);
+  msdf_probe_loss_k<<<1, ML_THREADS, 0, (hipStream_t)stream>>>(*a);
   return msdf_check_launch();
 }

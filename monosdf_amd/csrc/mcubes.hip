@@ -52,21 +52,6 @@ bool mc_dims_ok(int nx, int ny, int nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_inclusive_scan(T v) {
-  const int lane = lane_id();
-  for (int o = 1; o < 64; o <<= 1) {
-    const T u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 struct Grid {
   int nx, ny, nz;
   uint32_t sx, sy;                          // strides of axes 0 and 1 (axis 2: 1)
@@ -158,7 +143,7 @@ mc_scan_blocks_k(const uint32_t* __restrict__ counts, int64_t n_words, McWord* _
     sv += cv[q];
     st += ct[q];
   }
-  const uint32_t iv = wave_inclusive_scan(sv), it = wave_inclusive_scan(st);
+  const uint32_t iv = wave_incl_scan(sv), it = wave_incl_scan(st);
   if (lane_id() == 63) {
     wv[wave] = iv;
     wt[wave] = it;
@@ -197,7 +182,7 @@ mc_scan_top_k(int64_t* __restrict__ bsum, int64_t n_blocks, int64_t* __restrict_
   for (int64_t base = 0; base < n_blocks; base += 1024) {
     const int64_t b = base + threadIdx.x;
     const int64_t x = b < n_blocks ? bsum[2 * b] : 0, y = b < n_blocks ? bsum[2 * b + 1] : 0;
-    const int64_t ix = wave_inclusive_scan(x), iy = wave_inclusive_scan(y);
+    const int64_t ix = wave_incl_scan(x), iy = wave_incl_scan(y);
     if (lane_id() == 63) {
       wv[wave] = ix;
       wt[wave] = iy;
@@ -335,7 +320,7 @@ mc_emit_faces_k(const float* __restrict__ vol, Grid g, uint32_t n, float level, 
         ntri = MC_TRI_COUNT[code];
       }
     }
-    const int incl = wave_inclusive_scan(ntri);
+    const int incl = wave_incl_scan(ntri);
     size_t f = (size_t)(words[w].tbase + (uint32_t)(incl - ntri)) * 3;
     for (int t = 0; t < ntri; ++t) {
 #pragma unroll

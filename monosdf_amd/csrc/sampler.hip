@@ -23,30 +23,6 @@
 
 #define SMP_WAVES 4
 
-__device__ __forceinline__ float smp_scan_incl(float v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ float smp_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ float smp_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ float smp_density(const float s, const float beta) {
-  const float e = expm1f(-fabsf(s) / beta);
-  const float sg = (s > 0.f) ? 1.f : (s < 0.f) ? -1.f : 0.f;
-  return (1.0f / beta) * (0.5f + 0.5f * sg * e);
-}
 // torch.linspace(0, 1, n)[j] (symmetric evaluation, like ATen's kernel); one step is the start alone, as in ATen
 // (the step 1 / (n - 1) below would be infinite, and 1 - inf * 0 a NaN sample)
 __device__ __forceinline__ float smp_linspace01(const int j, const int n) {
@@ -56,6 +32,44 @@ __device__ __forceinline__ float smp_linspace01(const int j, const int n) {
 }
 
 typedef msdf_sampler_args_t SmpArgs;
+
+struct SmpRay {
+  float o[3], d[3];
+  __device__ __forceinline__ void point(const float z, float* p) const {
+    p[0] = o[0] + z * d[0]; p[1] = o[1] + z * d[1]; p[2] = o[2] + z * d[2];
+  }
+};
+__device__ __forceinline__ SmpRay smp_ray(const SmpArgs& a, const int ray) {
+  SmpRay r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { r.o[c] = a.ray_o[ray * 3 + c]; r.d[c] = a.ray_d[ray * 3 + c]; }
+  return r;
+}
+
+// The order of the stable counting ranks: v[k] stands before x, which stands at index j of v (equal values keep their
+// index order; with j past the end, x stands after all its equals).
+__device__ __forceinline__ int smp_before(const float vk, const int k, const float x, const int j) {
+  return (vk < x || (vk == x && k < j)) ? 1 : 0;
+}
+// `cnt` plus how many of v[0..n) stand before x.  The count goes on from `cnt`: with the rank added on afterwards the
+// compiler schedules the merge loop of smp_resample_k unlike the inline loop this replaces.
+__device__ __forceinline__ int smp_rank(const float* v, const int n, const float x, const int j, int cnt = 0) {
+  for (int k = 0; k < n; ++k) cnt += smp_before(v[k], k, x, j);
+  return cnt;
+}
+// the rank among all of v[0..n), and in `head` the rank among v[0..n_head) alone, in ONE loop (a second loop for it
+// made smp_finish_k spill scalar registers)
+__device__ __forceinline__ int smp_rank(const float* v, const int n, const float x, const int j, const int n_head,
+                                        int& head) {
+  int r = 0;
+  head = 0;
+  for (int k = 0; k < n; ++k) {
+    const int before = smp_before(v[k], k, x, j);
+    r += before;
+    head += (k < n_head) ? before : 0;
+  }
+  return r;
+}
 
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(64 * SMP_WAVES) smp_init_k(const SmpArgs a) {
@@ -67,14 +81,16 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_init_k(const SmpArgs a) {
     for (int i = lane; i < 2 * a.max_rounds; i += 64) a.flags[i] = 0u;
   if (ray == 0 && lane == 0 && a.h_saved != nullptr) a.h_saved[0] = 0u;     // set by msdf_sdf_forward_save, if it runs
   const int n = a.n_eval;
-  const float o0 = a.ray_o[ray * 3 + 0], o1 = a.ray_o[ray * 3 + 1], o2 = a.ray_o[ray * 3 + 2];
-  const float d0 = a.ray_d[ray * 3 + 0], d1 = a.ray_d[ray * 3 + 1], d2 = a.ray_d[ray * 3 + 2];
+  const SmpRay ry = smp_ray(a, ray);
   // slab test against the cube [-bound, bound]^3
-  const float ta0 = (-a.bound - o0) / (d0 + 1e-15f), tb0 = (a.bound - o0) / (d0 + 1e-15f);
-  const float ta1 = (-a.bound - o1) / (d1 + 1e-15f), tb1 = (a.bound - o1) / (d1 + 1e-15f);
-  const float ta2 = (-a.bound - o2) / (d2 + 1e-15f), tb2 = (a.bound - o2) / (d2 + 1e-15f);
-  float near_c = fmaxf(fmaxf(fminf(ta0, tb0), fminf(ta1, tb1)), fminf(ta2, tb2));
-  float far_c = fminf(fminf(fmaxf(ta0, tb0), fmaxf(ta1, tb1)), fmaxf(ta2, tb2));
+  float ta[3], tb[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ta[c] = (-a.bound - ry.o[c]) / (ry.d[c] + 1e-15f);
+    tb[c] = (a.bound - ry.o[c]) / (ry.d[c] + 1e-15f);
+  }
+  float near_c = fmaxf(fmaxf(fminf(ta[0], tb[0]), fminf(ta[1], tb[1])), fminf(ta[2], tb[2]));
+  float far_c = fminf(fminf(fmaxf(ta[0], tb[0]), fmaxf(ta[1], tb[1])), fmaxf(ta[2], tb[2]));
   if (far_c < near_c) far_c = 1e9f;
   // bound <= 0: no cube test, the constant far of UniformSampler(take_sphere_intersection=False) (ray_sampler.py:64-65)
   const float far = (a.bound > 0.f) ? fminf(far_c, a.far) : a.far;
@@ -96,14 +112,13 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_init_k(const SmpArgs a) {
     zrow[j] = z;
     a.new_z[(size_t)ray * n + j] = z;
     a.new_pos[(size_t)ray * n + j] = j;
-    float* p = a.pts + ((size_t)ray * n + j) * 3;
-    p[0] = o0 + z * d0; p[1] = o1 + z * d1; p[2] = o2 + z * d2;
+    ry.point(z, a.pts + ((size_t)ray * n + j) * 3);
     if (j + 1 < n) {
       const float dz = zfin(j + 1) - z;
       sumsq += dz * dz;
     }
   }
-  sumsq = smp_sum(sumsq);
+  sumsq = wave_sum(sumsq);
   if (lane == 0) {
     a.beta[ray] = sqrtf(a.lemma * sumsq);
     if (a.far_out != nullptr) a.far_out[ray] = far;
@@ -135,14 +150,19 @@ __device__ __forceinline__ bool smp_round_active(const SmpArgs& a) {
   return a.round_idx == 0 || a.flags[2 * (a.round_idx - 1) + 1] != 0u;
 }
 
+// a ray's z / sdf rows into the wave's LDS view
+__device__ __forceinline__ void smp_fill(const SmpLds& l, const float* zrow, const float* srow, const int M) {
+  for (int i = lane_id(); i < M; i += 64) { l.z[i] = zrow[i]; l.sdf[i] = srow[i]; }
+  smp_sync();
+}
+
 // load z / sdf of the ray (after scattering the freshly evaluated sdf values), build dists and d*
 __device__ __forceinline__ void smp_load_ray(const SmpArgs& a, const SmpLds& l, const int ray, const bool scatter) {
   const int lane = lane_id();
   const int M = a.M;
   const float* zrow = a.z + (size_t)ray * a.m_max;
   float* srow = a.sdf + (size_t)ray * a.m_max;
-  for (int i = lane; i < M; i += 64) { l.z[i] = zrow[i]; l.sdf[i] = srow[i]; }
-  smp_sync();
+  smp_fill(l, zrow, srow, M);
   if (scatter) {
     for (int j = lane; j < a.n_eval; j += 64)
       l.sdf[a.new_pos[(size_t)ray * a.n_eval + j]] = a.new_sdf[(size_t)ray * a.n_eval + j];
@@ -162,9 +182,7 @@ __device__ __forceinline__ void smp_load_ray(const SmpArgs& a, const SmpLds& l, 
       const float area = s * (s - aa) * (s - b) * (s - c);
       ds = (2.0f * sqrtf(area)) / aa;
     }
-    const float s0 = l.sdf[i], s1 = l.sdf[i + 1];
-    const float sg0 = (s0 > 0.f) ? 1.f : (s0 < 0.f) ? -1.f : 0.f;
-    const float sg1 = (s1 > 0.f) ? 1.f : (s1 < 0.f) ? -1.f : 0.f;
+    const float sg0 = sgnf(l.sdf[i]), sg1 = sgnf(l.sdf[i + 1]);   // before the store, which may alias them
     l.dist[i] = aa;
     const float dsv = (sg0 * sg1 == 1.f) ? ds : 0.f;
     l.dstar[i] = dsv;
@@ -184,11 +202,11 @@ __device__ __forceinline__ float smp_error_bound(const SmpLds& l, const int M, c
     float fe = 0.f, er = 0.f;
     if (ok) {
       const float d = l.dist[i];
-      fe = d * smp_density(l.sdf[i], beta);
+      fe = d * laplace_density(l.sdf[i], beta);
       er = expf(-l.dstar[i] / beta) * (d * d) * inv4b2;
     }
-    const float fe_incl = smp_scan_incl(fe);
-    const float er_incl = smp_scan_incl(er);
+    const float fe_incl = wave_incl_scan(fe);
+    const float er_incl = wave_incl_scan(er);
     if (ok) {
       const float integral = carry_fe + fe_incl - fe;          // exclusive
       const float errint = carry_err + er_incl;                // inclusive
@@ -198,7 +216,7 @@ __device__ __forceinline__ float smp_error_bound(const SmpLds& l, const int M, c
     carry_fe += __shfl(fe_incl, 63, 64);
     carry_err += __shfl(er_incl, 63, 64);
   }
-  return smp_max(best);
+  return wave_max(best);
 }
 
 __global__ void __launch_bounds__(64 * SMP_WAVES) smp_beta_k(const SmpArgs a) {
@@ -254,14 +272,11 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_resample_k(const SmpArgs a
     float fe = 0.f, er = 0.f;
     if (ok) {
       const float d = (i + 1 < M) ? l.dist[i] : 1e10f;
-      fe = d * smp_density(l.sdf[i], beta);
+      fe = d * laplace_density(l.sdf[i], beta);
       if (more && i + 1 < M) er = expf(-l.dstar[i] / beta) * (l.dist[i] * l.dist[i]) * inv4b2;
     }
-    float fprev = __shfl_up(fe, 1, 64);
-    if (lane == 0) fprev = 0.f;
-    const float fe_excl = smp_scan_incl(fprev);
-    const float fe_incl = fe_excl + fe;
-    const float er_incl = smp_scan_incl(er);
+    const float fe_excl = wave_excl_scan(fe);
+    const float er_incl = wave_incl_scan(er);
     if (ok && i + 1 < M) {
       const float trans = expf(-(carry_fe + fe_excl));
       float p;
@@ -270,10 +285,10 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_resample_k(const SmpArgs a
       l.tmp[i] = p;
       psum += p;
     }
-    carry_fe += __shfl(fe_incl, 63, 64);
+    carry_fe += __shfl(fe_excl + fe, 63, 64);      // lane 63: the chunk's sum, in one broadcast
     carry_err += __shfl(er_incl, 63, 64);
   }
-  psum = smp_sum(psum);
+  psum = wave_sum(psum);
   smp_sync();
   // cdf[0] = 0, cdf[i+1] = cumsum(pdf / sum)[i]  -> stored in dstar-independent buffer: reuse tmp shifted
   // (cdf kept in `dstar` array from here on: d* is no longer needed)
@@ -281,7 +296,7 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_resample_k(const SmpArgs a
   for (int base = 0; base < M - 1; base += 64) {
     const int i = base + lane;
     const float p = (i < M - 1) ? l.tmp[i] / psum : 0.f;
-    const float incl = smp_scan_incl(p);
+    const float incl = wave_incl_scan(p);
     if (i < M - 1) l.dstar[i + 1] = carry + incl;
     carry += __shfl(incl, 63, 64);
   }
@@ -317,8 +332,7 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_resample_k(const SmpArgs a
     return;
   }
   // merge: stable ranks by counting (robust even if the new samples are not perfectly monotone)
-  const float o0 = a.ray_o[ray * 3 + 0], o1 = a.ray_o[ray * 3 + 1], o2 = a.ray_o[ray * 3 + 2];
-  const float d0 = a.ray_d[ray * 3 + 0], d1 = a.ray_d[ray * 3 + 1], d2 = a.ray_d[ray * 3 + 2];
+  const SmpRay ry = smp_ray(a, ray);
   float* zrow = a.z + (size_t)ray * a.m_max;
   float* srow = a.sdf + (size_t)ray * a.m_max;
   for (int i = lane; i < M; i += 64) {
@@ -332,12 +346,11 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_resample_k(const SmpArgs a
     const float sj = l.snew[j];
     int cnt = 0;
     for (int i = 0; i < M; ++i) cnt += (l.z[i] <= sj) ? 1 : 0;
-    for (int k = 0; k < n_new; ++k) cnt += (l.snew[k] < sj || (l.snew[k] == sj && k < j)) ? 1 : 0;
+    cnt = smp_rank(l.snew, n_new, sj, j, cnt);
     zrow[cnt] = sj;
     a.new_z[(size_t)ray * a.n_eval + j] = sj;
     a.new_pos[(size_t)ray * a.n_eval + j] = cnt;
-    float* p = a.pts + ((size_t)ray * a.n_eval + j) * 3;
-    p[0] = o0 + sj * d0; p[1] = o1 + sj * d1; p[2] = o2 + sj * d2;
+    ry.point(sj, a.pts + ((size_t)ray * a.n_eval + j) * 3);
   }
 }
 
@@ -370,17 +383,12 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
     v[j] = x;
   }
   smp_sync();
-  const float o0 = a.ray_o[ray * 3 + 0], o1 = a.ray_o[ray * 3 + 1], o2 = a.ray_o[ray * 3 + 2];
-  const float d0 = a.ray_d[ray * 3 + 0], d1 = a.ray_d[ray * 3 + 1], d2 = a.ray_d[ray * 3 + 2];
+  const SmpRay ry = smp_ray(a, ray);
   for (int j = lane; j < S; j += 64) {
     const float x = v[j];
     // rn: the rank among the samples that are not dense-set columns (the first n_final + 2 entries of v)
-    int r = 0, rn = 0;
-    for (int k = 0; k < S; ++k) {
-      const int before = (v[k] < x || (v[k] == x && k < j)) ? 1 : 0;
-      r += before;
-      rn += (k < a.n_final + 2) ? before : 0;
-    }
+    int rn;
+    const int r = smp_rank(v, S, x, j, a.n_final + 2, rn);
     sorted[r] = x;
     a.z_out[(size_t)ray * S + r] = x;
     if (a.row_map != nullptr) {
@@ -391,10 +399,7 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
       const int er = (e >= 0) ? ray * a.n_extra + e : a.N * a.n_extra + ray * (S - a.n_extra) + rn;
       a.row_map[er] = ray * S + r;
     }
-    if (a.pts_out != nullptr) {
-      float* p = a.pts_out + ((size_t)ray * S + r) * 3;
-      p[0] = o0 + x * d0; p[1] = o1 + x * d1; p[2] = o2 + x * d2;
-    }
+    if (a.pts_out != nullptr) ry.point(x, a.pts_out + ((size_t)ray * S + r) * 3);
   }
   smp_sync();
   if (lane == 0) {
@@ -407,7 +412,8 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_finish_k(const SmpArgs a) 
       float* e = a.pts_out + (size_t)a.N * S * 3;
       if (a.row_map != nullptr)      // the eikonal block is evaluated where it stands
         for (int i = 0; i < 4; ++i) a.row_map[a.N * S + i * a.N + ray] = a.N * S + i * a.N + ray;
-      const float od[3] = {o0 + ze * d0, o1 + ze * d1, o2 + ze * d2};
+      float od[3];
+      ry.point(ze, od);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         float u = a.eik_uniform[(size_t)ray * 3 + c];
@@ -433,8 +439,7 @@ __global__ void __launch_bounds__(64 * SMP_WAVES) smp_error_bound_k(const float*
   if (ray >= N) return;
   const int lane = lane_id();
   const SmpLds l = smp_lds(smp_lds_mem, M, 0);
-  for (int i = lane; i < M; i += 64) { l.z[i] = z[(size_t)ray * M + i]; l.sdf[i] = sdf[(size_t)ray * M + i]; }
-  smp_sync();
+  smp_fill(l, z + (size_t)ray * M, sdf + (size_t)ray * M, M);
   for (int i = lane; i + 1 < M; i += 64) {
     l.dist[i] = l.z[i + 1] - l.z[i];
     l.dstar[i] = dstar[(size_t)ray * (M - 1) + i];
@@ -450,7 +455,7 @@ __global__ void __launch_bounds__(256) laplace_density_k(const float* __restrict
                                                          const int beta_stride, const int64_t n, const int cols,
                                                          float* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    out[i] = smp_density(sdf[i], beta[(i / cols) * beta_stride]);
+    out[i] = laplace_density(sdf[i], beta[(i / cols) * beta_stride]);
 }
 // g_sdf = g * d sigma / d s,  g_beta_part[i] = g * d sigma / d beta (summed per beta by the caller)
 __global__ void __launch_bounds__(256) laplace_density_bwd_k(const float* __restrict__ sdf, const float* __restrict__ beta,
@@ -461,7 +466,7 @@ __global__ void __launch_bounds__(256) laplace_density_bwd_k(const float* __rest
     const float s = sdf[i], b = beta[(i / cols) * beta_stride], gi = g[i];
     const float a = fabsf(s);
     const float ex = expf(-a / b);                       // d expm1(t)/dt = exp(t), t = -|s|/beta
-    const float sg = (s > 0.f) ? 1.f : (s < 0.f) ? -1.f : 0.f;
+    const float sg = sgnf(s);
     // sigma = (1/b)(1/2 + 1/2 sg expm1(-a/b));  |s|' = sg, sg^2 = 1 away from 0 (torch: sign(0) = 0 -> grad 0)
     g_sdf[i] = gi * (1.0f / b) * 0.5f * sg * ex * (-sg / b);
     const float em1 = expm1f(-a / b);
@@ -477,52 +482,46 @@ static int smp_check(const msdf_sampler_args_t* a) {
 static size_t smp_lds_bytes(const msdf_sampler_args_t* a) {
   return (size_t)SMP_WAVES * (5 * (a->m_max + 1) + a->n_eval) * sizeof(float);
 }
-template <typename K>
-static int smp_launch(K kernel, const msdf_sampler_args_t* a, size_t lds, void* stream) {
-  if (a->N == 0) return MSDF_OK;
+// one wave per ray; more than 48 KiB of LDS needs the opt-in, more than the 160 KiB of a compute unit cannot run
+template <typename K, typename... A>
+static int smp_launch(K kernel, int N, size_t lds, void* stream, const A&... args) {
+  if (N == 0) return MSDF_OK;
   if (lds > 160 * 1024) return MSDF_ERR_UNSUPPORTED;
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return MSDF_ERR_LAUNCH;
-  kernel<<<(a->N + SMP_WAVES - 1) / SMP_WAVES, 64 * SMP_WAVES, lds, (hipStream_t)stream>>>(*a);
+  kernel<<<(N + SMP_WAVES - 1) / SMP_WAVES, 64 * SMP_WAVES, lds, (hipStream_t)stream>>>(args...);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_sampler_init(const msdf_sampler_args_t* a, void* stream) {
   if (smp_check(a)) return MSDF_ERR_ARG;
-  return smp_launch(smp_init_k, a, 0, stream);
+  return smp_launch(smp_init_k, a->N, 0, stream, *a);
 }
 static int smp_round_check(const msdf_sampler_args_t* a) {
   return a->flags == nullptr || a->round_idx < 0 || a->round_idx >= a->max_rounds || a->M > a->m_max || a->M < 2;
 }
 extern "C" int msdf_sampler_beta(const msdf_sampler_args_t* a, void* stream) {
   if (smp_check(a) || smp_round_check(a)) return MSDF_ERR_ARG;
-  return smp_launch(smp_beta_k, a, smp_lds_bytes(a), stream);
+  return smp_launch(smp_beta_k, a->N, smp_lds_bytes(a), stream, *a);
 }
 extern "C" int msdf_sampler_resample(const msdf_sampler_args_t* a, void* stream) {
   if (smp_check(a) || smp_round_check(a) || a->n_final > a->n_eval) return MSDF_ERR_ARG;
-  return smp_launch(smp_resample_k, a, smp_lds_bytes(a), stream);
+  return smp_launch(smp_resample_k, a->N, smp_lds_bytes(a), stream, *a);
 }
 extern "C" int msdf_sampler_finish(const msdf_sampler_args_t* a, void* stream) {
   if (smp_check(a) || a->flags == nullptr || (a->extra_idx == nullptr && a->n_extra > 0) ||
       a->m_max < a->n_eval * a->max_rounds)
     return MSDF_ERR_ARG;
   const size_t lds = (size_t)SMP_WAVES * 2 * (a->n_final + a->n_extra + 2) * sizeof(float);
-  return smp_launch(smp_finish_k, a, lds, stream);
+  return smp_launch(smp_finish_k, a->N, lds, stream, *a);
 }
 
 extern "C" int msdf_sampler_error_bound(const float* z, const float* sdf, const float* dstar, const float* beta,
                                         int beta_stride, int N, int M, float* out, void* stream) {
   if (N < 0 || M < 2 || (beta_stride != 0 && beta_stride != 1)) return MSDF_ERR_ARG;
-  if (N == 0) return MSDF_OK;
   const size_t lds = (size_t)SMP_WAVES * 5 * (M + 1) * sizeof(float);
-  if (lds > 160 * 1024) return MSDF_ERR_UNSUPPORTED;
-  if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)smp_error_bound_k,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return MSDF_ERR_LAUNCH;
-  smp_error_bound_k<<<(N + SMP_WAVES - 1) / SMP_WAVES, 64 * SMP_WAVES, lds, (hipStream_t)stream>>>(
-      z, sdf, dstar, beta, beta_stride, N, M, out);
-  return msdf_check_launch();
+  return smp_launch(smp_error_bound_k, N, lds, stream, z, sdf, dstar, beta, beta_stride, N, M, out);
 }
 
 static int dens_grid(int64_t n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }

@@ -9,12 +9,6 @@
 // Layers without weight norm (has_g == 0) pass through.
 #include "common.h"
 
-__device__ __forceinline__ float wn_wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(256)
 msdf_weightnorm_forward_k(const msdf_wn_layer_t* __restrict__ layers, const int* __restrict__ row_layer,
                           const int total_rows, float* __restrict__ flat_w, float* __restrict__ flat_b,
@@ -30,7 +24,7 @@ msdf_weightnorm_forward_k(const msdf_wn_layer_t* __restrict__ layers, const int*
   if (L.has_g) {
     float ss = 0.f;
     for (int c = lane; c < L.cols; c += 64) ss += v[c] * v[c];
-    const float n = sqrtf(wn_wave_sum(ss));
+    const float n = sqrtf(wave_sum(ss));
     scale = L.g[r] / n;
     if (lane == 0) norms[row_g] = n;
   }
@@ -58,7 +52,7 @@ msdf_weightnorm_backward_k(const msdf_wn_layer_t* __restrict__ layers, const int
   }
   float dot = 0.f;
   for (int c = lane; c < L.cols; c += 64) dot += dw[c] * v[c];
-  dot = wn_wave_sum(dot);
+  dot = wave_sum(dot);
   const float n = norms[row_g];
   const float g = L.g[r];
   const float a = g / n, bq = g * dot / (n * n * n);
