@@ -1,0 +1,194 @@
+"""The fused MLP kernels against the exact answer, bit for bit, on all three matrix cores.
+
+tests/mlp_exact_cases.py builds integer ReLU networks on which every sum the kernels form is exact in fp32 -- in any order,
+on the fp32 matrix instructions and as bf16 plane products -- and certifies that on the float64 operands of every product.
+Here the real modules (RenderingNetwork, ImplicitNetwork, set_precision) run those cases and every output, input gradient
+and weight gradient is compared with torch.equal: a lost plane product, a wrong tile, a padded slot that leaks or a
+gradient column far below the tensor's maximum all show, which the 1e-4 max-norm bar of the parity tests does not see.
+
+A case runs on a core only where its certificate holds (the bf16x3 core forms three of the nine plane products); the fp32
+and bf16x6 cores run every case, and test_every_core_runs_every_kind asserts what is left for bf16x3."""
+import pytest
+import torch
+
+import mlp_exact_cases as mx
+
+pytestmark = pytest.mark.gpu
+
+
+def _certified(name, core):
+    case = mx.ALL_CASES[name]
+    cert = mx.certificate(case, core)
+    if core != 'bf16x3':
+        assert cert.ok, (name, core, cert.failures[:3])
+    mx.assert_reaches(name, core)
+    return case, cert.ok
+
+
+def _same(name, core, key, got, want):
+    want32 = want.float()
+    assert torch.equal(want32.double(), want), (name, key, 'the reference is no fp32 value')
+    got = got.detach().cpu()
+    assert got.dtype == torch.float32 and got.shape == want32.shape, (name, core, key, got.dtype, got.shape, want32.shape)
+    if not torch.equal(got, want32):
+        raise AssertionError('%s on %s: %s differs from the exact result, first at %r'
+                             % (name, core, key, mx.first_difference(got, want32)))
+
+
+def _color_net(case, core):
+    from monosdf_amd.model.network import RenderingNetwork
+    a = case.args
+    net = RenderingNetwork(a['F'], a['mode'], 9 if a['mode'] == 'idr' else 3, 3, [a['width']] * a['hidden'],
+                           weight_norm=False, multires_view=0, per_image_code=a['code'], if_hdr=True)
+    net.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
+    net = net.cuda()
+    net.set_precision(core)
+    return net
+
+
+def _run_color(name, core):
+    case, ok = _certified(name, core)
+    if not ok:
+        return False
+    a, i = case.args, case.inputs
+    net = _color_net(case, core)
+    feat = i['feat'].cuda().requires_grad_()
+    nrm = i['normals'].cuda().requires_grad_()
+    rgb = net(i['points'].cuda(), nrm, i['dirs'].cuda(), feat, i['indices'].cuda(), if_pixel_input=True,
+              samples_per_ray=a['spr'] if a['spr'] > 1 else None)['rgb']
+    (rgb * case.up['g_rgb'].cuda()).sum().backward()
+    ref = mx.reference(case)
+    got = {'rgb': rgb, 'g_feat': feat.grad}
+    if a['mode'] == 'idr':
+        got['g_nrm'] = nrm.grad
+    else:
+        assert nrm.grad is None
+    for k, p in net.named_parameters():
+        got['g_code' if k == 'embeddings' else k] = p.grad
+    assert set(got) == set(ref)
+    for k in ref:
+        _same(name, core, k, got[k], ref[k])
+    return True
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.COLOR_CASES))
+def test_color_network_exact(name, core):
+    """Forward, the gradients of features, normals and per-image code, and every weight and bias gradient: widths 64, 48
+    (odd last tile), 100 (padded slots), 176 (several pairs per chunk), 256 (K = 16); one to three hidden layers; idr and
+    nerf; with and without the code; 256 and 40 features; 7 samples per ray; P of every wave and workgroup edge; ReLU
+    inputs of exactly zero in hidden and output layers."""
+    _run_color('color.' + name, core)
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.PROBE_CASES))
+def test_plane_probes(name, core):
+    """One- to three-plane weights, features and upstream gradients: between them every kept plane product of b16_step
+    carries a result bit in the forward and in the transposed product (test_mlp_exact_cases_cpu.py shows that each one,
+    removed, changes a result)."""
+    _run_color('probe.' + name, core)
+
+
+def _sdf_net(case, core):
+    from monosdf_amd.model.network import ImplicitNetwork
+    a = case.args
+    net = ImplicitNetwork(a['F'], 0.0, 3, 1, [a['width']] * a['hidden'], geometric_init=False, skip_in=(),
+                          weight_norm=False, multires=0)
+    net.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
+    net = net.cuda()
+    net.set_precision(core)
+    return net
+
+
+def _run_sdf(name, core):
+    case, ok = _certified(name, core)
+    if not ok:
+        return False
+    net = _sdf_net(case, core)
+    ref = mx.reference(case)
+    x = case.inputs['x'].cuda()
+    # forward(): the output layer as a matrix product; gradient_sdf(): the sdf row as a dot product, no features;
+    # get_sdf_vals() without autograd: the forward-only kernel
+    out = net(x)
+    _same(name, core, 'forward().sdf', out[:, :1], ref['sdf'])
+    _same(name, core, 'forward().feat', out[:, 1:], ref['feat'])
+    _same(name, core, 'gradient_sdf()', net.gradient_sdf(x), ref['grad'])
+    with torch.no_grad():
+        _same(name, core, 'get_sdf_vals()', net.get_sdf_vals(x), ref['sdf'])
+    # all three outputs of one evaluation and the double backward to every parameter
+    sdf, feat, grad = net.get_outputs(x)
+    for k, t in (('sdf', sdf), ('feat', feat), ('grad', grad)):
+        _same(name, core, k, t, ref[k])
+    up = {k: v.cuda() for k, v in case.up.items()}
+    ((up['a'] * sdf).sum() + (up['B'] * feat).sum() + (up['C'] * grad).sum()).backward()
+    params = dict(net.named_parameters())
+    assert set(params) == set(case.state)
+    for k, p in params.items():
+        _same(name, core, k, p.grad, ref[k])
+    return True
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.SDF_CASES))
+def test_sdf_network_exact(name, core):
+    """forward(), gradient_sdf(), get_sdf_vals() and the double backward of <a, sdf> + <B, feat> + <C, d sdf/dx> to every
+    weight and bias: widths 64, 48, 100, 256 (17 out tiles, K = 17 transposed), two and three hidden layers, P of every
+    wave and workgroup edge.  Needs exp2 to give 1 for -0 and 0 below -288 (softplus is then ReLU exactly)."""
+    _run_sdf('sdf.' + name, core)
+
+
+def _grid_net(case, core):
+    from monosdf_amd.model.network import ImplicitNetworkGrid
+    a, g = case.args, mx.GRID
+    net = ImplicitNetworkGrid(a['F'], 0.0, 3, 1, [a['width']] * a['hidden'], geometric_init=False, skip_in=(),
+                              weight_norm=False, multires=0, base_size=g['base_size'], end_size=g['end_size'],
+                              logmap=g['logmap'], num_levels=g['num_levels'], level_dim=g['level_dim'],
+                              divide_factor=g['divide_factor'])
+    state = {k: v.clone() for k, v in case.state.items()}
+    state['encoding.offsets'] = net.encoding.offsets.clone()
+    net.load_state_dict(state, strict=True)
+    net = net.cuda()
+    net.set_precision(core)
+    return net
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.GRID_CASES))
+def test_hash_grid_model_exact(name, core):
+    """ImplicitNetworkGrid end to end -- encoder, network, the grid part of d sdf/dx, the double backward with the table
+    gradient -- on four dense levels of scale 8 with points on multiples of 1/8.  The fp32 core reads the encoder's
+    level-major tensors and applies its Jacobian inside the kernels; the bf16 cores read rows."""
+    name = 'grid.' + name
+    case, ok = _certified(name, core)
+    assert ok, (name, core)
+    net = _grid_net(case, core)
+    ref = mx.reference(case)
+    x = case.inputs['x'].cuda()
+    out = net(x)
+    _same(name, core, 'forward().sdf', out['sdf'], ref['sdf'])
+    _same(name, core, 'forward().feature', out['feature'], ref['feat'])
+    _same(name, core, 'gradient_sdf()', net.gradient_sdf(x), ref['grad'])
+    with torch.no_grad():
+        _same(name, core, 'get_sdf_vals()', net.get_sdf_vals(x), ref['sdf'])
+    sdf, feat, grad = net.get_outputs(x)
+    for k, t in (('sdf', sdf), ('feat', feat), ('grad', grad)):
+        _same(name, core, k, t, ref[k])
+    up = {k: v.cuda() for k, v in case.up.items()}
+    ((up['a'] * sdf).sum() + (up['B'] * feat).sum() + (up['C'] * grad).sum()).backward()
+    params = dict(net.named_parameters())
+    assert set(params) == set(case.state)
+    for k, p in params.items():
+        _same(name, core, k, p.grad, ref[k])
+
+
+def test_every_core_runs_every_kind():
+    """fp32 and bf16x6 are certified on every case; bf16x3 on at least one full colour case (forward, backward, weight
+    gradients), one full SDF case and the probes that need no more than its three plane products."""
+    for core in ('fp32', 'bf16x6'):
+        bad = [n for n, c in mx.ALL_CASES.items() if not mx.certificate(c, core).ok]
+        assert not bad, (core, bad)
+    ok3 = [n for n, c in mx.ALL_CASES.items() if mx.certificate(c, 'bf16x3').ok]
+    for kind in ('color.', 'sdf.', 'probe.', 'grid.'):
+        assert any(n.startswith(kind) for n in ok3), kind
+    assert {'probe.w2f1g1', 'probe.w1f2g1', 'probe.w1f1g2'} <= set(ok3)

@@ -1,0 +1,296 @@
+"""tests/mlp_exact_cases.py on the CPU: the cases keep their conditions, the certificate accepts them and rejects
+hand-made violations, an emulation of the three matrix cores reproduces the float64 reference bit for bit on every
+certified product, and the probe cases have teeth -- each kept plane product, k tile, out tile and point, removed,
+changes a result."""
+import pytest
+import torch
+
+import mlp_exact_cases as mx
+
+NAMES = list(mx.ALL_CASES)
+# what the two-plane core is certified on: everything whose products need no more than (1,1), (1,2), (2,1)
+X3_NOT_CERTIFIED = {'color.w64_h2_idr_big_p65', 'probe.w3f1g1', 'probe.w1f3g1', 'probe.w1f1g3', 'probe.w2f2g1',
+                    'probe.w2f1g2', 'probe.h2_w1f3g1', 'probe.h2_w1f1g3'}
+P_EDGES = {1, 15, 16, 17, 63, 64, 65, 213}
+
+
+# ---- the cases ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', NAMES)
+def test_products_amount_to_the_reference(name):
+    """The pass written product by product (what the certificate looks at) gives exactly what float64 autograd gives."""
+    case = mx.ALL_CASES[name]
+    _, out, _ = mx.products(case)
+    ref = mx.reference(case)
+    assert set(out) == set(ref)
+    for k in ref:
+        assert out[k].shape == ref[k].shape and torch.equal(out[k], ref[k]), (name, k)
+        assert torch.equal(ref[k].float().double(), ref[k]), (name, k, 'not an fp32 value')
+
+
+def test_cases_cover_the_sizes_and_options():
+    for cases in (mx.COLOR_CASES, mx.SDF_CASES):
+        assert P_EDGES <= {c.args['P'] for c in cases.values()}
+    col = [c.args for c in mx.COLOR_CASES.values()]
+    assert {a['width'] for a in col} >= {64, 48, 100, 176, 256} and {a['hidden'] for a in col} == {1, 2, 3}
+    assert {a['mode'] for a in col} == {'idr', 'nerf'} and {a['code'] for a in col} == {True, False}
+    assert 256 in {a['F'] for a in col} and any(a['F'] % 16 for a in col)
+    assert any(a['spr'] == 7 and a['P'] % 64 and a['P'] > 128 for a in col)
+    sdf = [c.args for c in mx.SDF_CASES.values()]
+    assert {a['width'] for a in sdf} >= {64, 48, 100, 256} and {a['hidden'] for a in sdf} == {2, 3}
+
+
+@pytest.mark.parametrize('name', ['sdf.' + n for n in mx.SDF_CASES] + ['grid.' + n for n in mx.GRID_CASES])
+def test_sdf_inputs_keep_softplus_at_relu(name):
+    case = mx.ALL_CASES[name]
+    hid = case.args['hidden']
+    for l in range(hid):
+        W, b = case.state['lin%d.weight' % l], case.state['lin%d.bias' % l]
+        assert torch.equal(W % 4, torch.zeros_like(W)) and torch.equal(b % 4, torch.full_like(b, 2))
+    x = case.inputs['x']
+    if case.kind == 'grid':
+        # points on multiples of 1/8 inside [-1, 1], both kinds of position (on a node, half-way) and both ends; integer
+        # tables; first-layer weights multiples of 32; dense levels of scale 8
+        W0, emb = case.state['lin0.weight'], case.state['encoding.embeddings']
+        assert torch.equal(W0 % 32, torch.zeros_like(W0)) and torch.equal(emb, emb.round())
+        assert x.abs().max() <= 1 and ((8 * x) % 2 == 0).any() and ((8 * x) % 2 == 1).any()
+        x = 8 * x
+        geo = mx.hg.level_geometry(mx.GRID)
+        assert geo['S'] == 0.0 and all(mx.hg.level_scale(geo, l) == (8.0, 9) for l in range(geo['L']))
+        assert [geo['offsets'][l + 1] - geo['offsets'][l] for l in range(geo['L'])] == [729] * geo['L']
+    assert torch.equal(x, x.round())
+    pre = mx.products(case)[2]
+    assert len(pre) == hid and not mx.check_preactivations(pre)
+    for a in pre:                                       # both sides of the switch in every layer
+        assert (a >= 2).any() and (a <= -2).any()
+
+
+@pytest.mark.parametrize('name', ['w64_h1_idr_p213', 'w48_h2_idr_p65', 'w64_h2_idr_code_spr7_p217', 'w64_h3_nerf_p15'])
+def test_color_cases_hold_relu_ties(name):
+    """Hidden and output pre-activations of exactly zero (mask h > 0 / y > 0: zero on both sides), next to both signs."""
+    pre = mx.products(mx.COLOR_CASES[name])[2]
+    for a in pre:
+        assert (a == 0).any() and (a > 0).any() and (a < 0).any()
+
+
+# ---- the certificate ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', NAMES)
+def test_certificate_accepts_the_cases(name):
+    case = mx.ALL_CASES[name]
+    for core in ('fp32', 'bf16x6'):
+        cert = mx.certificate(case, core)
+        assert cert.ok, (core, cert.failures[:3])
+    assert mx.certificate(case, 'bf16x3').ok == (name not in X3_NOT_CERTIFIED)
+
+
+def test_every_core_has_a_full_case_of_every_kind():
+    ok3 = [n for n in NAMES if mx.certificate(mx.ALL_CASES[n], 'bf16x3').ok]
+    for kind in ('color.', 'sdf.', 'probe.', 'grid.'):
+        assert any(n.startswith(kind) for n in ok3)
+    # a full case: forward, transposed and weight-gradient products, all of them certified
+    for n in ('color.w100_h2_idr_code_f40_p63', 'sdf.w48_h3_f24_p65'):
+        assert n in ok3 and {p.role for p in mx.products(mx.ALL_CASES[n])[0]} == {'forward', 'transposed', 'wgrad', 'dot'}
+
+
+def _product(A, B, unit='core', adds=()):
+    t = lambda v: torch.tensor(v, dtype=torch.float64)
+    return mx.Product('hand', 'forward', unit, t(A), t(B), tuple(t(a) for a in adds), None)
+
+
+def test_certificate_rejects_a_sum_over_the_bound():
+    fits = _product([[2.0 ** 23, 2.0 ** 23 - 1]], [[1.0], [1.0]])
+    over = _product([[2.0 ** 23 + 1, 2.0 ** 23 - 1]], [[1.0], [1.0]])
+    for core in mx.CORES:
+        assert not mx.check_product(fits, 'fp32')
+        assert any('2^24' in w for w in mx.check_product(over, core)), core
+    # the granule counts: the same magnitudes in steps of 1/8 are eight times too many
+    assert mx.check_product(_product([[2.0 ** 21, 2.0 ** 21 + 0.125]], [[1.0], [4.0]]), 'fp32')
+    assert not mx.check_product(_product([[2.0 ** 19, 2.0 ** 18 + 0.125]], [[1.0], [4.0]]), 'fp32')
+    # ... and the summand a product starts from or ends with
+    assert mx.check_product(_product([[2.0 ** 23 + 1]], [[1.0]], adds=[[[2.0 ** 23 - 1]]]), 'fp32')
+    assert not mx.check_product(_product([[2.0 ** 23 + 1]], [[1.0]], adds=[[[2.0 ** 23 - 2]]]), 'fp32')
+    # a whole case: three-plane weights against three-plane features
+    case = mx.color_case('over', wp=3, fp=3, P=17, in_max=1, seed=7)
+    for core in mx.CORES:
+        assert not mx.certificate(case, core).ok
+
+
+def test_certificate_rejects_plane_products_a_core_does_not_form():
+    two_by_two = _product([[257.0]], [[257.0]])
+    assert not mx.check_product(two_by_two, 'fp32') and not mx.check_product(two_by_two, 'bf16x6')
+    assert any('(2, 2)' in w for w in mx.check_product(two_by_two, 'bf16x3'))
+    # the weight-gradient kernel of bf16x6 is the fp32 one, that of bf16x3 forms the same three products
+    assert not mx.check_product(two_by_two._replace(unit='wgrad'), 'bf16x6')
+    assert mx.check_product(two_by_two._replace(unit='wgrad'), 'bf16x3')
+    assert not mx.check_product(two_by_two._replace(unit='dot'), 'bf16x3')
+    two_by_three = _product([[257.0]], [[131329.0]])
+    assert any('(2, 3)' in w for w in mx.check_product(two_by_three, 'bf16x6'))
+    assert not mx.check_product(_product([[1.0]], [[131329.0]]), 'bf16x6')
+    assert not mx.check_product(_product([[131329.0]], [[3.0]]), 'bf16x6')
+    cert = mx.certificate(mx.PROBE_CASES['w2f2g1'], 'bf16x3')
+    assert not cert.ok and any(w.startswith('u0.fwd') and '(2, 2)' in w for w in cert.failures)
+    # not an fp32 value at all
+    assert mx.check_product(_product([[2.0 ** 24 + 1]], [[1.0]]), 'fp32')
+
+
+@pytest.mark.parametrize('bias', [0.0, 1.0, -1.0, 0.5])
+def test_certificate_rejects_a_preactivation_near_the_switch(bias):
+    base = mx.SDF_CASES['w64_h2_p15']
+    state = dict(base.state)
+    state['lin0.bias'] = torch.full_like(state['lin0.bias'], bias)      # a = 4 k + bias
+    case = base._replace(state=state)
+    for core in mx.CORES:
+        cert = mx.certificate(case, core)
+        assert not cert.ok and any(w.startswith('layer 0') for w in cert.failures)
+
+
+def test_plane_units_have_the_planes_they_are_named_for():
+    for n, unit in mx.PLANE_UNIT.items():
+        for k in (1, 2, 3, -1, -3):
+            planes = mx.split_planes(torch.tensor([k * unit]))
+            assert [bool(p.any()) for p in planes] == [i < n for i in range(3)], (n, k)
+            assert sum(p.double() for p in planes).item() == k * unit
+
+
+# ---- emulation of the cores ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', NAMES)
+def test_emulated_cores_equal_the_reference_on_certified_products(name):
+    case = mx.ALL_CASES[name]
+    for core in mx.CORES:
+        for pr in mx.products(case)[0]:
+            if mx.check_product(pr, core):
+                continue
+            exact = mx.want(pr)
+            for seed in (1, 2):
+                got = mx.emulate(pr, core, seed=seed)
+                assert torch.equal(got.double(), exact), (name, core, pr.name, mx.first_difference(got, exact))
+
+
+def test_an_uncertified_product_is_not_exact():
+    """The plane condition is needed: where the certificate names a missing plane product, the emulation is off."""
+    for name, product, core in (('w2f2g1', 'u0.fwd', 'bf16x3'), ('w3f1g1', 'u0.bwd', 'bf16x3'),
+                                ('w1f3g1', 'u0.fwd', 'bf16x3')):
+        pr = [p for p in mx.products(mx.PROBE_CASES[name])[0] if p.name == product][0]
+        assert mx.check_product(pr, core)
+        assert not torch.equal(mx.emulate(pr, core).double(), mx.want(pr))
+        assert torch.equal(mx.emulate(pr, 'bf16x6').double(), mx.want(pr))
+
+
+# ---- teeth --------------------------------------------------------------------------------------------------------
+def _changed_by(drop, core, role, cases):
+    """The (case, product) pairs, certified on this core, whose emulated result changes when `drop` is lost."""
+    hit = []
+    for name, case in cases.items():
+        if not mx.certificate(case, core).ok:
+            continue
+        for pr in mx.products(case)[0]:
+            if pr.role == role and mx.arithmetic(pr.unit, core) and \
+                    not torch.equal(mx.emulate(pr, core, drop=drop).double(), mx.want(pr)):
+                hit.append((name, pr.name))
+    return hit
+
+
+@pytest.mark.parametrize('core,role', [('bf16x3', 'forward'), ('bf16x3', 'transposed'), ('bf16x3', 'wgrad'),
+                                       ('bf16x6', 'forward'), ('bf16x6', 'transposed')])
+def test_every_kept_plane_product_carries_a_result_bit(core, role):
+    """b16_step without one of its lines (three for bf16x3, six for bf16x6): a probe case certified on that core changes,
+    in the forward product, in a transposed one and (bf16x3: its own weight-gradient kernel) in a weight gradient."""
+    for pair in mx.KEPT[mx.PLANES[core]]:
+        assert _changed_by(('pair', pair), core, role, mx.PROBE_CASES), (core, role, pair)
+
+
+def test_probes_reach_the_first_layers_feature_product():
+    """... and it is the product the probes are built around that notices: weights x features, weights^T x a-bar."""
+    want = {('bf16x6', 'forward', (1, 3)): ('w1f3g1', 'u0.fwd'), ('bf16x6', 'forward', (3, 1)): ('w3f1g1', 'u0.fwd'),
+            ('bf16x6', 'forward', (2, 2)): ('w2f2g1', 'u0.fwd'), ('bf16x6', 'transposed', (3, 1)): ('w3f1g1', 'u0.bwd'),
+            ('bf16x6', 'transposed', (1, 3)): ('w1f1g3', 'u0.bwd'), ('bf16x6', 'transposed', (2, 2)): ('w2f1g2', 'u0.bwd'),
+            ('bf16x3', 'forward', (1, 2)): ('w1f2g1', 'u0.fwd'), ('bf16x3', 'forward', (2, 1)): ('w2f1g1', 'u0.fwd'),
+            ('bf16x3', 'transposed', (1, 2)): ('w1f1g2', 'u0.bwd'), ('bf16x3', 'transposed', (2, 1)): ('w2f1g1', 'u0.bwd'),
+            ('bf16x3', 'wgrad', (1, 2)): ('w1f2g1', 'u0.wgrad'), ('bf16x3', 'wgrad', (2, 1)): ('w1f1g2', 'u0.wgrad')}
+    for (core, role, pair), hit in want.items():
+        assert hit in _changed_by(('pair', pair), core, role, mx.PROBE_CASES), (core, role, pair)
+    # the hidden product behind a first layer that hands it two- and three-plane activations, and its transpose
+    for core, role, pair, hit in (('bf16x6', 'forward', (1, 3), ('h2_w1f3g1', 'u2.fwd')),
+                                  ('bf16x6', 'forward', (1, 2), ('h2_w1f3g1', 'u2.fwd')),
+                                  ('bf16x6', 'transposed', (1, 3), ('h2_w1f1g3', 'u2.bwd')),
+                                  ('bf16x3', 'forward', (1, 2), ('h2_w1f2g1', 'u2.fwd')),
+                                  ('bf16x3', 'transposed', (1, 2), ('h2_w1f1g2', 'u2.bwd'))):
+        assert hit in _changed_by(('pair', pair), core, role, mx.PROBE_CASES), (core, role, pair)
+
+
+@pytest.mark.parametrize('name', ['color.w100_h2_idr_code_f40_p63', 'sdf.w48_h3_f24_p65', 'probe.w2f1g1'])
+@pytest.mark.parametrize('core', mx.CORES)
+def test_a_lost_tile_or_point_changes_the_result(name, core):
+    """One k tile, one out tile or one point dropped from a product of a matrix core: the result differs wherever the
+    dropped part contributes at all, and every out tile and every point does."""
+    case = mx.ALL_CASES[name]
+    for pr in mx.products(case)[0]:
+        if pr.unit != 'core':
+            continue
+        exact = mx.want(pr)
+        contributes = lambda A, B: bool((A @ B).any())
+        m, k = pr.A.shape
+        n = pr.B.shape[1]
+        live = 0
+        for t in range(-(-k // 16)):
+            s = slice(16 * t, 16 * t + 16)
+            changed = not torch.equal(mx.emulate(pr, core, drop=('ktile', t)).double(), exact)
+            assert changed == contributes(pr.A[:, s], pr.B[s]), (pr.name, 'k tile', t)
+            live += changed
+        assert live >= 1, pr.name
+        for t in range(-(-m // 16)):
+            s = slice(16 * t, 16 * t + 16)
+            changed = not torch.equal(mx.emulate(pr, core, drop=('otile', t)).double(), exact)
+            assert changed == contributes(pr.A[s], pr.B), (pr.name, 'out tile', t)
+            if pr.role == 'forward' and pr.name != 'out.fwd':
+                assert changed, (pr.name, 'out tile', t)
+        for p in sorted({0, n // 2, n - 1}):
+            changed = not torch.equal(mx.emulate(pr, core, drop=('point', p)).double(), exact)
+            assert changed == contributes(pr.A, pr.B[:, p:p + 1]), (pr.name, 'point', p)
+            if pr.role == 'forward' and pr.name.endswith('.fwd'):
+                assert changed, (pr.name, 'point', p)
+
+
+# ---- structure ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('core', mx.CORES)
+def test_cases_reach_the_branches_they_are_named_for(core):
+    for name in mx.REACHES:
+        mx.assert_reaches(name, core)
+    kernels, flags = set(), set()
+    for name, case in mx.ALL_CASES.items():
+        for d in mx.structure(case, core).values():
+            kernels.add(d['kernel'])
+            flags |= {k for k in ('odd_last_tile', 'dead_pair', 'partial_last_chunk') if d[k]}
+            if core == 'fp32' and d['pairs_per_chunk'] > 1:
+                flags.add('chunks=%d' % d['chunks'] if d['chunks'] > 1 else 'one chunk')
+    if core == 'fp32':
+        assert kernels == {'gemm_tiles<3,4>', 'gemm_tiles<5,3>', 'gemm_tiles<16,1>', 'gemm_tiles<17,1>', 'gemm_tiles<0,1>'}
+        assert {'chunks=2', 'one chunk'} <= flags
+    else:
+        ns = mx.PLANES[core]
+        assert kernels == {'gemm_b16<%d,%d>' % (ns, k) for k in (0, 2, 3, 8, 9)}
+    assert {'odd_last_tile', 'dead_pair'} <= flags and (('partial_last_chunk' in flags) == (core != 'bf16x6'))
+
+
+def test_structure_follows_the_plans():
+    """structure() reads the tile counts from the plans of monosdf_amd/plan.py, not from the case names."""
+    case = mx.SDF_CASES['w256_h2_f256_p17']
+    mp = mx.build_plan(case)
+    assert [(mp.plan.layer[l].kt, mp.plan.layer[l].ot, mp.plan.layer[l].ktp, mp.plan.layer[l].otp) for l in range(3)] == \
+        [(3, 16, 3, 16), (16, 16, 16, 16), (16, 17, 16, 17)]
+    p16 = mp.build_b16(3)
+    assert [(p16.layer[l].ktp, p16.layer[l].otp) for l in range(3)] == [(2, 8), (8, 8), (8, 9)]
+    st = mx.structure(case, 'fp32')
+    assert st['out.fwd']['chunks'] == 9 and st['out.fwd']['pairs'] == 9 and st['l0.fwd']['pairs_per_chunk'] == 4
+
+
+def test_first_difference_names_the_slot():
+    want = torch.zeros(130, 48)
+    assert mx.first_difference(want.clone(), want) is None
+    got = want.clone()
+    got[77, 39] = 1.0
+    got[100, 2] = 1.0
+    d = mx.first_difference(got, want)
+    assert (d['row'], d['column'], d['workgroup'], d['wave'], d['tile'], d['quarter'], d['component']) == (77, 39, 1, 0, 2, 1, 3)
+    assert d['n_different'] == 2 and d['got'] == 1.0 and d['want'] == 0.0
+    assert mx.first_difference(torch.zeros(3), torch.zeros(4)) == dict(shape=((3,), (4,)))
+    assert mx.first_difference(torch.tensor([0.0, 2.0]), torch.tensor([0.0, 1.0]))['row'] == 1
