@@ -280,6 +280,11 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def addr(t):
+    """Device address of a tensor for a pointer field of an argument struct (None -> NULL)."""
+    return None if t is None else t.data_ptr()
+
+
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -6,7 +6,9 @@ The batch-global convergence test (``beta.max() > beta0``, reference ray_sampler
 device: the kernels of a round return at once when the previous round did not ask for them, so the host may
 enqueue rounds without reading the flags back (``speculate``), and only has to check afterwards that it
 enqueued enough of them."""
+import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -24,6 +26,70 @@ def _need_gpu(t):
     return t.detach().float().contiguous()
 
 
+# -- what one sampler call points at: every pointer field of msdf_sampler_args_t, stated once -------------------------
+# The sizes of a call: N rays, n_eval new samples per round, n_final importance samples, n_extra columns of the dense
+# set, K = max_total_iters rounds at the most; S is the width of the final set (with near and far).
+class _Sizes(collections.namedtuple('_Sizes', 'N n_eval n_final n_extra K training want_points')):
+    S = property(lambda d: d.n_final + d.n_extra + 2)
+
+
+_F32, _I32 = torch.float32, torch.int32
+# buffers the call allocates: field -> (shape from the _Sizes, dtype); a shape of None: this call has no such buffer and
+# the field is NULL
+ALLOCATED = {
+    'z': (lambda d: (d.N, d.n_eval * d.K), _F32),
+    'sdf': (lambda d: (d.N, d.n_eval * d.K), _F32),
+    'new_z': (lambda d: (d.N, d.n_eval), _F32),
+    'new_pos': (lambda d: (d.N, d.n_eval), _I32),
+    'pts': (lambda d: (d.N * d.n_eval, 3), _F32),
+    'beta': (lambda d: (d.N,), _F32),
+    'flags': (lambda d: (2 * d.K,), _I32),                # zeroed by msdf_sampler_init
+    'final_z': (lambda d: (d.N, d.n_final), _F32),
+    'z_out': (lambda d: (d.N, d.S), _F32),
+    'z_eik': (lambda d: (d.N, 1), _F32),
+    # the ray samples' points and, in training, the four eikonal points of every ray behind them
+    'pts_out': (lambda d: (d.N * d.S + (4 * d.N if d.training else 0), 3) if d.want_points else None, _F32),
+    'far_out': (lambda d: (d.N, 1), _F32),                # UniformSampler only
+}
+# inputs the caller supplies: the rays, beta0, the draws, the dense-set columns, the pass's SdfReuse, a round's SDF
+# values
+SUPPLIED = ('ray_o', 'ray_d', 'beta0', 'new_sdf', 'jitter', 'u_final', 'extra_idx', 'eik_idx', 'eik_u', 'eik_uniform',
+            'nei_rand', 'row_map', 'h_saved')
+# outputs of the kernels that only tests ask for
+LEFT_NULL = ('dbg_dstar', 'dbg_err0', 'dbg_cdf', 'rounds_out')
+
+
+class _SamplerCall:
+    """The msdf_sampler_args_t of one call and every tensor whose address sits in it: they live as long as this does."""
+
+    def __init__(self, sizes, device, **scalars):
+        self.sizes, self.device, self.held, self.stream = sizes, device, {}, _lib.stream_ptr()
+        a = self.args = _lib.SamplerArgs()
+        a.N, a.n_eval, a.n_final, a.n_extra = sizes.N, sizes.n_eval, sizes.n_final, sizes.n_extra
+        a.max_rounds, a.m_max, a.training = sizes.K, sizes.n_eval * sizes.K, int(sizes.training)
+        for name, value in scalars.items():
+            setattr(a, name, value)
+
+    def bind(self, **tensors):
+        """Pointer fields from tensors (None -> NULL)."""
+        for name, t in tensors.items():
+            setattr(self.args, name, _lib.addr(t))
+            self.held[name] = t
+
+    def alloc(self, *names):
+        """The call's own buffers, from the table, bound; returns them in the order asked for."""
+        new = {}
+        for name in names:
+            shape, dtype = ALLOCATED[name]
+            shape = shape(self.sizes)
+            new[name] = None if shape is None else torch.empty(*shape, device=self.device, dtype=dtype)
+        self.bind(**new)
+        return list(new.values())
+
+    def launch(self, entry):
+        _lib.call(entry, C.byref(self.args), self.stream)
+
+
 class UniformSampler(RaySampler):
     """reference ray_sampler.py:16-83: N_samples equidistant depths between near and far (far = the exit of the
     cube [-R, R]^3 clipped to 2 R 1.75 with take_sphere_intersection, else that constant), stratified jitter in
@@ -39,27 +105,17 @@ class UniformSampler(RaySampler):
         ray_dirs, cam_loc = _need_gpu(ray_dirs), _need_gpu(cam_loc)
         dev = ray_dirs.device
         N, n = ray_dirs.shape[0], self.N_samples
-        f32 = dict(device=dev, dtype=torch.float32)
         if model.training and jitter is None:
-            jitter = torch.rand(N, n, **f32)
-        z = torch.empty(N, n, **f32)
-        far = torch.empty(N, 1, **f32)
-        scratch = torch.empty(N * n * 5 + N, **f32)        # new_z, pts, beta of the shared kernel: not returned
-        a = _lib.SamplerArgs()
-        a.ray_o, a.ray_d, a.N = cam_loc.data_ptr(), ray_dirs.data_ptr(), N
-        a.M, a.m_max, a.n_eval, a.n_final, a.n_extra = n, n, n, 0, 0
-        a.max_rounds = 1
-        a.near, a.far = float(self.near), float(self.far)
-        a.bound = float(self.scene_bounding_sphere) if self.take_sphere_intersection else 0.0
-        a.lemma = 1.0
-        a.z, a.new_z = z.data_ptr(), scratch.data_ptr()
-        a.new_pos = scratch.data_ptr() + 4 * N * n
-        a.pts, a.beta = scratch.data_ptr() + 8 * N * n, scratch.data_ptr() + 20 * N * n
-        a.jitter = _need_gpu(jitter).data_ptr() if jitter is not None else None
-        a.far_out = far.data_ptr()
-        _lib.call('msdf_sampler_init', C.byref(a), _lib.stream_ptr())
-        self._keep = (jitter, scratch)
-        return z, torch.full((N, 1), float(self.near), **f32), far
+            jitter = torch.rand(N, n, device=dev, dtype=torch.float32)
+        # the first step of an error-bound call of one round with no final set: its n_eval samples are the result
+        bound = float(self.scene_bounding_sphere) if self.take_sphere_intersection else 0.0
+        call = _SamplerCall(_Sizes(N, n, 0, 0, 1, False, False), dev, near=float(self.near), far=float(self.far),
+                            bound=bound, lemma=1.0)
+        call.bind(ray_o=cam_loc, ray_d=ray_dirs, jitter=None if jitter is None else _need_gpu(jitter))
+        z, far = call.alloc('z', 'far_out')
+        call.alloc('new_z', 'new_pos', 'pts', 'beta')        # msdf_sampler_init writes them too: not returned
+        call.launch('msdf_sampler_init')
+        return z, torch.full((N, 1), float(self.near), device=dev, dtype=torch.float32), far
 
 
 class ErrorBoundSampler(RaySampler):
@@ -218,6 +274,64 @@ class ErrorBoundSampler(RaySampler):
             return self.max_total_iters
         return max(self._hist[which]) if self._hist[which] else 1
 
+    @staticmethod
+    def _draws(noise, d, device):
+        """The random numbers of a training call: (name -> fp32 tensor, whether 'eik_uniform' is still U[0,1)).
+        ONE launch for every draw of the call: stratified jitter, inverse-CDF u, neighbour jitter, the eikonal sample's
+        column ('eik_u'; floor(u S) in the finish kernel: the reference's randint, ray_sampler.py:254) and the uniform
+        eikonal points ((2u - 1) R in the finish kernel: the reference's uniform_(-R, R), network.py:587).  A draw that
+        model._noise injects takes its name's place and no part of the pool; an injected 'eik_idx' is a column already
+        and stays in the noise."""
+        f32 = dict(device=device, dtype=torch.float32)
+        # in the order the pool is cut
+        shapes = {'jitter': (d.N, d.n_eval), 'final_u': (d.N, d.n_final), 'nei_rand': (2 * d.N, 3), 'eik_idx': (d.N,),
+                  'eik_uniform': (d.N, 3)}
+        if not d.want_points:
+            del shapes['nei_rand'], shapes['eik_uniform']
+        need = [k for k in shapes if noise.get(k) is None]
+        pool = torch.rand(sum(math.prod(shapes[k]) for k in need), **f32) if need else None
+        draws, off = {}, 0
+        for k, shape in shapes.items():
+            if k in need:
+                n = math.prod(shape)
+                draws['eik_u' if k == 'eik_idx' else k] = pool[off:off + n].view(shape)
+                off += n
+            elif k != 'eik_idx':
+                draws[k] = noise[k].to(**f32).contiguous()
+        return draws, 'eik_uniform' in need
+
+    def _finish_inputs(self, call, noise, draws, extra_idx):
+        """Everything the finish kernel needs -- none of it depends on the number of rounds -- issued while the
+        GPU is still busy with the first round, so that after a host sync only the launch is left.  Returns the
+        kernel's outputs (z_out, z_eik, pts_out or None)."""
+        d, dev = call.sizes, call.device
+        eik_idx = noise.get('eik_idx')
+        if eik_idx is None and 'eik_u' not in draws:
+            eik_idx = torch.randint(d.S, (d.N,), device=dev)
+        if eik_idx is not None:
+            eik_idx = eik_idx.to(device=dev, dtype=torch.int64).contiguous()
+        if extra_idx is None:
+            extra_idx = self._extra_columns(d.training, noise, dev)[0]
+        call.bind(eik_idx=eik_idx, eik_u=draws.get('eik_u'), eik_uniform=draws.get('eik_uniform'),
+                  nei_rand=draws.get('nei_rand'), extra_idx=extra_idx)
+        return call.alloc('z_out', 'z_eik', 'pts_out')
+
+    def _round(self, call, k, net, speculate, save_for):
+        """Round k of the call: the SDF at the new points, beta and the convergence flag, the next samples."""
+        pts, flags = call.held['pts'], call.held['flags']
+        # fused forward kernel on the new points, [N*n_eval, 1]; in a speculated round it returns at once when the
+        # previous round did not ask for this one
+        run_flag = flags.data_ptr() + 4 * (2 * k - 1) if (speculate > 0 and k > 0) else None
+        call.bind(new_sdf=net._sdf_only(pts, run_flag=run_flag, save_for=save_for))
+        call.args.M, call.args.round_idx = call.sizes.n_eval * (k + 1), k
+        call.launch('msdf_sampler_beta')
+        group = self.global_rounds
+        if group is not None:
+            # bits of a positive float order like the float: an integer MAX over ranks is the batch's max beta
+            import torch.distributed as dist
+            dist.all_reduce(flags[2 * k:2 * k + 1], op=dist.ReduceOp.MAX, group=None if group is True else group)
+        call.launch('msdf_sampler_resample')
+
     def sample(self, ray_dirs, cam_loc, model, want_points=True, speculate=0, beta0=None, sdf_reuse=None):
         """get_z_vals plus (optionally) the 3-D points of the ray samples and, in training, the eikonal
         points appended behind them -- written by the finish kernel instead of ~15 small tensor ops.
@@ -234,138 +348,44 @@ class ErrorBoundSampler(RaySampler):
         dev = ray_dirs.device
         ray_dirs, cam_loc = _need_gpu(ray_dirs), _need_gpu(cam_loc)
         self._resolve()               # bookkeeping of the previous call (its flags arrived long ago)
-        N = ray_dirs.shape[0]
-        n_eval, n_final, n_extra = self.N_samples_eval, self.N_samples, self.N_samples_extra
         K = self.max_total_iters
-        m_max = n_eval * K
-        S = n_final + n_extra + 2
+        d = _Sizes(ray_dirs.shape[0], self.N_samples_eval, self.N_samples, self.N_samples_extra, K,
+                   bool(model.training), bool(want_points))
         noise = getattr(model, '_noise', None) or {}
-        training = bool(model.training)
-        net = model.implicit_network
         beta0 = (model.density.get_beta() if beta0 is None else beta0).detach().float().reshape(1).contiguous()
-        f32 = dict(device=dev, dtype=torch.float32)
-        z = torch.empty(N, m_max, **f32)
-        sdf = torch.empty(N, m_max, **f32)
-        new_z = torch.empty(N, n_eval, **f32)
-        new_pos = torch.empty(N, n_eval, device=dev, dtype=torch.int32)
-        pts = torch.empty(N * n_eval, 3, **f32)
-        beta = torch.empty(N, **f32)
-        flags = torch.empty(2 * K, device=dev, dtype=torch.int32)        # zeroed by msdf_sampler_init
-        final_z = torch.empty(N, n_final, **f32)
-        jitter = u_final = nei_drawn = eik_u_drawn = eik_unit_drawn = None
-        if training:
-            # ONE launch for every random draw of the call: stratified jitter, inverse-CDF u, neighbour jitter, the
-            # eikonal sample's column (floor(u S): the reference's randint, ray_sampler.py:254) and the uniform
-            # eikonal points ((2u - 1) R inside the finish kernel: the reference's uniform_(-R, R), network.py:587)
-            need = [k for k in ('jitter', 'final_u', 'nei_rand', 'eik_idx', 'eik_uniform') if noise.get(k) is None]
-            sizes = {'jitter': N * n_eval, 'final_u': N * n_final, 'nei_rand': 6 * N if want_points else 0,
-                     'eik_idx': N, 'eik_uniform': 3 * N if want_points else 0}
-            pool = torch.rand(sum(sizes[k] for k in need), **f32) if need else None
-            drawn, off = {}, 0
-            for k in need:
-                drawn[k] = pool[off:off + sizes[k]]
-                off += sizes[k]
-            jitter = noise.get('jitter')
-            jitter = drawn['jitter'].view(N, n_eval) if jitter is None else jitter.to(**f32).contiguous()
-            u_final = noise.get('final_u')
-            u_final = drawn['final_u'].view(N, n_final) if u_final is None else u_final.to(**f32).contiguous()
-            nei_drawn = drawn.get('nei_rand')
-            eik_u_drawn, eik_unit_drawn = drawn.get('eik_idx'), drawn.get('eik_uniform')
-        a = _lib.SamplerArgs()
-        a.ray_o, a.ray_d, a.N = cam_loc.data_ptr(), ray_dirs.data_ptr(), N
-        a.m_max, a.n_eval, a.n_final, a.n_extra = m_max, n_eval, n_final, n_extra
-        a.max_rounds, a.training, a.beta_iters = K, int(training), self.beta_iters
-        a.near, a.far, a.bound = float(self.near), float(self.far), float(self.scene_bounding_sphere)
-        a.eps, a.add_tiny, a.lemma = float(self.eps), float(self.add_tiny), self._lemma
-        a.beta0, a.z, a.sdf = beta0.data_ptr(), z.data_ptr(), sdf.data_ptr()
-        a.new_z, a.new_pos, a.pts, a.beta = new_z.data_ptr(), new_pos.data_ptr(), pts.data_ptr(), beta.data_ptr()
-        a.flags = flags.data_ptr()
-        a.jitter = jitter.data_ptr() if jitter is not None else None
-        a.u_final = u_final.data_ptr() if u_final is not None else None
-        a.final_z = final_z.data_ptr()
-        extra_idx = col_slot = None
+        call = _SamplerCall(d, dev, beta_iters=self.beta_iters, near=float(self.near), far=float(self.far),
+                            bound=float(self.scene_bounding_sphere), eps=float(self.eps),
+                            add_tiny=float(self.add_tiny), lemma=self._lemma)
+        draws, call.args.eik_unit = self._draws(noise, d, dev) if d.training else ({}, False)
+        call.bind(ray_o=cam_loc, ray_d=ray_dirs, beta0=beta0, jitter=draws.get('jitter'), u_final=draws.get('final_u'))
+        pts, flags = call.alloc('pts', 'flags')
+        call.alloc('z', 'sdf', 'new_z', 'new_pos', 'beta', 'final_z')
+        extra_idx = save_for = None
         if sdf_reuse is not None:
-            assert want_points and (sdf_reuse.N, sdf_reuse.S, sdf_reuse.n_extra) == (N, S, n_extra)
-            assert sdf_reuse.P == N * S + (4 * N if training else 0)
-            sdf_reuse.flags = flags
-            sdf_reuse.round_pts = pts      # the points of the last round that ran (the first: what the saved rows hold)
-            a.row_map, a.h_saved = sdf_reuse.row_map.data_ptr(), sdf_reuse.h_saved.data_ptr()
+            assert want_points and (sdf_reuse.N, sdf_reuse.S, sdf_reuse.n_extra) == (d.N, d.S, d.n_extra)
+            assert sdf_reuse.P == d.N * d.S + (4 * d.N if d.training else 0)
+            sdf_reuse.attach_sampler(flags, pts)
+            call.bind(row_map=sdf_reuse.row_map, h_saved=sdf_reuse.h_saved)
             if sdf_reuse.n_reuse > 0 and speculate in (0, 1):
-                extra_idx, col_slot = self._extra_columns(training, noise, dev, want_slots=True)
-        st = _lib.stream_ptr()
-        a.M = n_eval
-        _lib.call('msdf_sampler_init', C.byref(a), st)
-        z_out = z_eik = x_all = eik_idx = None
-
-        def prepare_finish():
-            """Everything the finish kernel needs -- none of it depends on the number of rounds -- issued while the
-            GPU is still busy with the first round, so that after a host sync only the launch is left."""
-            nonlocal z_out, z_eik, x_all, extra_idx, eik_idx
-            eik_idx = noise.get('eik_idx')
-            a.eik_u, a.eik_unit = None, 0
-            if eik_idx is None and eik_u_drawn is not None:
-                a.eik_idx, a.eik_u = None, eik_u_drawn.data_ptr()        # the column is floor(u S), formed in the kernel
-            else:
-                if eik_idx is None:
-                    eik_idx = torch.randint(S, (N,), device=dev)
-                eik_idx = eik_idx.to(device=dev, dtype=torch.int64).contiguous()
-                a.eik_idx = eik_idx.data_ptr()
-            z_out = torch.empty(N, S, **f32)
-            z_eik = torch.empty(N, 1, **f32)
-            a.z_out, a.z_eik, a.pts_out = z_out.data_ptr(), z_eik.data_ptr(), None
-            if want_points:
-                n_eik = 4 * N if training else 0
-                x_all = torch.empty(N * S + n_eik, 3, **f32)
-                a.pts_out = x_all.data_ptr()
-                if training:
-                    R = self.scene_bounding_sphere
-                    eik_uniform = noise.get('eik_uniform')
-                    if eik_uniform is None and eik_unit_drawn is not None and eik_unit_drawn.numel() == 3 * N:
-                        eik_uniform, a.eik_unit = eik_unit_drawn.view(N, 3), 1       # U[0,1): scaled to the cube in the kernel
-                    else:
-                        eik_uniform = (torch.empty(N, 3, **f32).uniform_(-R, R) if eik_uniform is None
-                                       else eik_uniform.to(**f32).contiguous())
-                    nei = noise.get('nei_rand')
-                    nei = nei_drawn.view(2 * N, 3) if nei is None else nei.to(**f32).contiguous()
-                    a.eik_uniform, a.nei_rand = eik_uniform.data_ptr(), nei.data_ptr()
-                    self._keep = (eik_uniform, nei)
-            if extra_idx is None:
-                extra_idx = self._extra_columns(training, noise, dev)[0]
-            a.extra_idx = extra_idx.data_ptr()
-
-        group = self.global_rounds
+                extra_idx, col_slot = self._extra_columns(d.training, noise, dev, want_slots=True)
+                if col_slot is not None:
+                    save_for = (sdf_reuse, col_slot, d.n_eval)
+        call.launch('msdf_sampler_init')
         # one all-reduce is enqueued per enqueued round, so the count must be the same on every rank of the group: the
         # caller's guess comes from guess_rounds(), which in this mode looks only at the history of all-reduced
         # decisions -- identical on every rank as long as the ranks make their group calls in lockstep (they must:
         # each one is a collective).  Round 3 enqueued all max_total_iters rounds here: K - 1 idle rounds and
         # collectives per call in the usual one-round state.
-        which = 1 if group is not None else 0
-        rounds = 0
+        which = 1 if self.global_rounds is not None else 0
         with torch.no_grad():
-            while True:
-                # fused forward kernel on the new points, [N*n_eval, 1]; in a speculated round it returns at once
-                # when the previous round did not ask for this one
-                run_flag = flags.data_ptr() + 4 * (2 * rounds - 1) if (speculate > 0 and rounds > 0) else None
-                save_for = (sdf_reuse, col_slot, n_eval) if (rounds == 0 and col_slot is not None) else None
-                new_sdf = net._sdf_only(pts, run_flag=run_flag, save_for=save_for)
-                a.new_sdf = new_sdf.data_ptr()
-                a.M, a.round_idx = n_eval * (rounds + 1), rounds
-                _lib.call('msdf_sampler_beta', C.byref(a), st)
-                if group is not None:
-                    # bits of a positive float order like the float: an integer MAX over ranks is the batch's max beta
-                    import torch.distributed as dist
-                    dist.all_reduce(flags[2 * rounds:2 * rounds + 1], op=dist.ReduceOp.MAX,
-                                    group=None if group is True else group)
-                _lib.call('msdf_sampler_resample', C.byref(a), st)
-                if rounds == 0:
-                    prepare_finish()
+            self._round(call, 0, model.implicit_network, speculate, save_for)
+            # behind the first round's launches, before any host read of the flags (see _finish_inputs)
+            z_out, z_eik, x_all = self._finish_inputs(call, noise, draws, extra_idx)
+            rounds = 1
+            # speculating: as many rounds as asked for; else the one host sync of the round
+            while (rounds < min(speculate, K)) if speculate > 0 else bool(flags[2 * rounds - 1].item()):
+                self._round(call, rounds, model.implicit_network, speculate, None)
                 rounds += 1
-                if speculate > 0:
-                    more = rounds < min(speculate, K)
-                else:
-                    more = bool(flags[2 * rounds - 1].item())         # the one host sync of the round
-                if not more:
-                    break
         self._pending = None
         self.stats['calls'] += 1
         if speculate > 0:
@@ -377,5 +397,5 @@ class ErrorBoundSampler(RaySampler):
         else:
             self._note_rounds(rounds, which)
         # final set: 64 importance samples + near + far + 32 columns of the dense set
-        _lib.call('msdf_sampler_finish', C.byref(a), st)
+        call.launch('msdf_sampler_finish')
         return z_out, z_eik, x_all

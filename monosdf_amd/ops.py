@@ -31,11 +31,6 @@ def _cont(t):
     return None if t is None else t.contiguous()
 
 
-def _addr(t):
-    """Device address of a tensor for a pointer field of an argument struct (None -> NULL)."""
-    return None if t is None else t.data_ptr()
-
-
 # matrix core of the fused MLP kernels (include/monosdf_plan.h MSDF_PRECISION_*)
 PRECISIONS = ('fp32', 'bf16x3', 'bf16x6')      # index = MSDF_PRECISION_*
 _PLANES = {'bf16x3': 2, 'bf16x6': 3}
@@ -192,7 +187,7 @@ class WeightNormTables:
             v = next(it)
             g = next(it) if has_g else None
             b = next(it)
-            r.v, r.g, r.b = v.data_ptr(), _addr(g), b.data_ptr()
+            r.v, r.g, r.b = v.data_ptr(), _lib.addr(g), b.data_ptr()
             r.rows, r.cols = rows, cols
             r.w_off, r.b_off, r.row_off, r.has_g = w_off, b_off, b_off, int(has_g)
             recs.append(bytes(r))
@@ -317,11 +312,16 @@ class SdfReuse:
             if REUSE_SAMPLER_H else None
         self.row_map = torch.empty(max(self.P, 1), device=device, dtype=torch.int32)
         self.h_saved = torch.empty(1, device=device, dtype=torch.int32)       # zeroed by msdf_sampler_init
-        self.flags = None                # the sampler's round flags (set by the sampler)
-        self.round_pts = None            # the sampler's point buffer [N n_eval, 3] (set by the sampler; for tests)
+        self.flags = self.round_pts = None        # the sampler's part: attach_sampler()
         self.n_split = N * S
         # whole workgroups of reused rows; the rows behind them are computed (again) by the node
         self.n_reuse = (N * n_extra) // 64 * 64 if REUSE_SAMPLER_H else 0
+
+    def attach_sampler(self, flags, pts):
+        """What the sampler call of the pass contributes: its round flags [2 max_total_iters] and its point buffer
+        [N n_eval, 3] -- the points of the last round that ran (the first: what the saved rows hold; for tests).  The
+        SDF node takes no SdfReuse this has not been called on."""
+        self.flags, self.round_pts = flags, pts
 
 
 def sdf_forward_save(mlp, wpack, bpack, x, clamp_radius, sphere_scale, run_flag, reuse, col_slot, n_cols):
@@ -403,10 +403,10 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     r_aux = torch.empty(*aux_shape, device=dev, dtype=torch.float32) if has_aux else None
     clamped = torch.empty(max(P, 1), device=dev, dtype=torch.uint8)
     a = _lib.FgArgs()
-    a.wpack, a.bpack, a.x, a.aux = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr(), _addr(aux)
+    a.wpack, a.bpack, a.x, a.aux = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr(), _lib.addr(aux)
     a.P, a.P_pad, a.n_clamp, a.n_feat = P, P_pad, n_clamp, n_feat
     a.clamp_radius, a.sphere_scale = float(clamp_radius), float(sphere_scale)
-    a.sdf, a.feat, a.nrm, a.r_aux, a.clamped = sdf.data_ptr(), feat.data_ptr(), nrm.data_ptr(), _addr(r_aux), \
+    a.sdf, a.feat, a.nrm, a.r_aux, a.clamped = sdf.data_ptr(), feat.data_ptr(), nrm.data_ptr(), _lib.addr(r_aux), \
         clamped.data_ptr()
     base = ws.data_ptr()
     a.H = base + 4 * woff['H']
@@ -422,7 +422,7 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     if reuse is not None:
         a.row_map, a.n_reuse = reuse.row_map.data_ptr(), reuse.n_reuse
         a.smp_flags, a.h_saved = reuse.flags.data_ptr(), reuse.h_saved.data_ptr()
-        a.h_stage, a.stage_pad = _addr(reuse.stage), reuse.stage_pad
+        a.h_stage, a.stage_pad = _lib.addr(reuse.stage), reuse.stage_pad
         a.wg_first = _fg_wg_first(reuse)
         saved += (reuse.row_map,)
     if P > 0:
@@ -450,18 +450,18 @@ def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=Non
     b = _lib.BwArgs()
     b.aux_C, b.aux_LC = state.aux_lm
     if state.jac_scale is not None:
-        b.dy_dx, b.aux_dx_scale, b.gg_out = dy_dx.data_ptr(), state.jac_scale, _addr(gg_out)
+        b.dy_dx, b.aux_dx_scale, b.gg_out = dy_dx.data_ptr(), state.jac_scale, _lib.addr(gg_out)
     b.wpack, b.bpack, b.x = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr()
     b.P, b.P_pad, b.n_feat, b.n_split = P, P_pad, state.n_feat, state.n_split
-    b.g_sdf, b.g_sdf_b, b.g_nrm, b.g_nrm_b = _addr(g_sdf), _addr(g_sdf_b), _addr(g_nrm), _addr(g_nrm_b)
-    b.g_feat = _addr(g_feat) if state.n_feat > 0 else None
-    b.g_raux = _addr(g_raux) if state.has_aux else None
+    b.g_sdf, b.g_sdf_b, b.g_nrm, b.g_nrm_b = _lib.addr(g_sdf), _lib.addr(g_sdf_b), _lib.addr(g_nrm), _lib.addr(g_nrm_b)
+    b.g_feat = _lib.addr(g_feat) if state.n_feat > 0 else None
+    b.g_raux = _lib.addr(g_raux) if state.has_aux else None
     b.clamped = clamped.data_ptr()
     b.row_map = row_map[0].data_ptr() if row_map else None
     base = ws.data_ptr()
     for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST'):
         setattr(b, k, base + 4 * woff[k])
-    b.g_aux = _addr(g_aux)
+    b.g_aux = _lib.addr(g_aux)
     if P > 0:
         _lib.call('msdf_sdf_backward', C.byref(mlp.plan), C.byref(b), _lib.stream_ptr())
         start_side_work(dev)                 # the colour network's queued weight-gradient launch, if any
@@ -660,7 +660,7 @@ class ColorMlpFunction(torch.autograd.Function):
         a = _lib.ColorFwdArgs()
         a.wpack, a.bpack = wpack.data_ptr(), bpack.data_ptr()
         a.x, a.dirs, a.nrm, a.feat = x.data_ptr(), dirs.data_ptr(), nrm.data_ptr(), feat.data_ptr()
-        a.code = _addr(code) if has_code else None
+        a.code = _lib.addr(code) if has_code else None
         a.P, a.P_pad, a.spr, a.save = P, P_pad, int(spr), 1 if save else 0
         a.rgb = rgb.data_ptr()
         base = ws.data_ptr()
@@ -693,7 +693,7 @@ class ColorMlpFunction(torch.autograd.Function):
         b.H, b.AB = base + 4 * woff['H'], base + 4 * woff['AB']
         b.g_feat, b.g_misc = g_feat.data_ptr(), g_misc.data_ptr()
         g_nrm = torch.empty(P, 3, device=dev, dtype=torch.float32) if plan.mode == 1 else None
-        b.g_nrm = _addr(g_nrm)
+        b.g_nrm = _lib.addr(g_nrm)
         if P > 0:
             _lib.call('msdf_color_backward', C.byref(plan), C.byref(b), _lib.stream_ptr())
             grad = cmlp.run_wgrad(P_pad, {'ws': ws, 'feat': feat}, defer=USE_SIDE_STREAM)
@@ -754,7 +754,7 @@ class CompositeFunction(torch.autograd.Function):
         a.z, a.sdf, a.rgb, a.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
         a.beta, a.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
         a.depth_scale_stride = ds_stride
-        a.depth_vals = _addr(depth_vals)
+        a.depth_vals = _lib.addr(depth_vals)
         a.N, a.S, a.white_bkgd = N, S, 1 if white_bkgd else 0
         a.bg0, a.bg1, a.bg2 = [float(v) for v in bg]
         a.weights, a.rgb_values, a.depth_values = weights.data_ptr(), rgb_values.data_ptr(), depth_values.data_ptr()
@@ -791,7 +791,8 @@ class CompositeFunction(torch.autograd.Function):
         b.z, b.sdf, b.rgb, b.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
         b.beta, b.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
         b.weights, b.wsum, b.depth_values = weights.data_ptr(), wsum.data_ptr(), depth_values.data_ptr()
-        b.g_rgb_values, b.g_depth, b.g_normal, b.g_weights = _addr(g_rgbv), _addr(g_depth), _addr(g_nmap), _addr(g_w)
+        b.g_rgb_values, b.g_depth = _lib.addr(g_rgbv), _lib.addr(g_depth)
+        b.g_normal, b.g_weights = _lib.addr(g_nmap), _lib.addr(g_w)
         b.N, b.S, b.white_bkgd = N, S, 1 if ctx.white_bkgd else 0
         b.bg0, b.bg1, b.bg2 = ctx.bg
         b.g_sdf, b.g_rgb, b.g_nrm, b.g_beta_part = g_sdf.data_ptr(), g_rgb.data_ptr(), g_nrm.data_ptr(), \

@@ -347,6 +347,62 @@ def test_global_round_decision_single_rank():
             dist.destroy_process_group()
 
 
+@pytest.mark.parametrize('with_reuse', [False, True])
+@pytest.mark.parametrize('speculate', [0, 1])
+def test_uninjected_draws_replayed(speculate, with_reuse):
+    """The draws sample() makes when nothing is injected: ONE torch.rand on the device, cut in the order jitter,
+    final_u, nei_rand, eik_idx, eik_uniform, and max_total_iters randperm rows on the CPU generator.  Drawn again
+    from the same seed in this test, cut the same way and injected, they give the same samples bit for bit (the
+    eikonal column floor(u S) and the eikonal points (2u - 1) R are formed here as the finish kernel forms them).
+    Sizes: 10 rays (off the 4 rays of a workgroup), 66 dense samples (over one 64-lane trip), no cut of the pool
+    on a round number, 10 * 7 = 70 >= 64 dense-set points so that an SdfReuse has rows to reuse and the column
+    table is drawn before the first launch."""
+    from monosdf_amd.conf import ConfigTree
+    from monosdf_amd.model.network import MonoSDFNetwork
+    from oracle import config, synth
+    N, n_eval, n_final, n_extra, K, seed = 10, 66, 33, 7, 2, 1234
+    S = n_final + n_extra + 2
+    conf = config.mlp_config(64, 8, beta=0.1)
+    conf['ray_sampler'].update(N_samples_eval=n_eval, N_samples=n_final, N_samples_extra=n_extra, max_total_iters=K)
+    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
+    m.load_state_dict(synth.make_state(conf, seed=5, jitter=0.3), strict=True)
+    m = m.cuda().train()
+    smp, net = m.ray_sampler, m.implicit_network
+    assert (smp.N_samples_eval, smp.N_samples, smp.N_samples_extra, smp.max_total_iters) == (n_eval, n_final, n_extra, K)
+    rays = synth.make_rays(N, seed=13, random_pose=True)
+    d, o = rays['ray_dirs'].cuda().contiguous(), rays['ray_cam_loc'].cuda().contiguous()
+    dev = d.device
+    R = float(conf['scene_bounding_sphere'])
+
+    def sample():
+        reuse = net.sdf_reuse(dev, N, S, n_extra, 4 * N, True) if with_reuse else None
+        assert not with_reuse or reuse.n_reuse == 64
+        z, z_eik, x_all = smp.sample(d, o, m, want_points=True, speculate=speculate, sdf_reuse=reuse)
+        assert speculate == 0 or smp.confirm()
+        return z.clone(), z_eik.clone(), x_all.clone(), smp.last_rounds
+
+    net.share(dev)
+    try:
+        torch.manual_seed(seed)
+        m._noise = None
+        drawn = sample()
+        torch.manual_seed(seed)
+        sizes = [N * n_eval, N * n_final, 6 * N, N, 3 * N]
+        jitter, final_u, nei, u_idx, u_eik = torch.rand(sum(sizes), device=dev).split(sizes)
+        m._noise = {'jitter': jitter.view(N, n_eval), 'final_u': final_u.view(N, n_final), 'nei_rand': nei.view(2 * N, 3),
+                    'eik_idx': torch.floor(u_idx * float(S)).clamp(max=S - 1).to(torch.int64),
+                    'eik_uniform': ((2.0 * u_eik - 1.0) * R).view(N, 3),
+                    'extra_idx': torch.stack([torch.randperm(n_eval * (k + 1))[:n_extra] for k in range(K)])}
+        assert m._noise['eik_uniform'].dtype == torch.float32 and m._noise['extra_idx'].shape == (K, n_extra)
+        injected = sample()
+    finally:
+        net.unshare()
+    assert drawn[0].shape == (N, S) and drawn[1].shape == (N, 1) and drawn[2].shape == (N * S + 4 * N, 3)
+    for name, a, b in zip(('z_vals', 'z_eik', 'x_all'), drawn, injected):
+        assert torch.equal(a, b), name
+    assert drawn[3] == injected[3] and 1 <= drawn[3] <= K
+
+
 def test_weight_norm_backward_checks_parameter_versions():
     """the weight-norm backward kernel re-reads weight_v / weight_g; an in-place update between forward
     and backward must raise (autograd's version counter) instead of returning gradients of other weights."""

@@ -57,6 +57,33 @@ def test_struct_sizes_match_header():
         assert ctypes.sizeof(cls) == sizes[n], (n, ctypes.sizeof(cls), sizes[n])
 
 
+def test_sampler_call_table_names_every_pointer_field():
+    """model/ray_sampler.py states what a sampler call points at once: every pointer field of msdf_sampler_args_t is
+    a buffer the call allocates, an input the caller supplies or a field left NULL -- exactly one of the three -- and
+    every allocated buffer has an extent at the smallest sizes the kernels take."""
+    from monosdf_amd import _lib
+    from monosdf_amd.model import ray_sampler as rs
+    pointers = {name for name, ctype in _lib.SamplerArgs._fields_ if ctype is ctypes.c_void_p}
+    kinds = [set(rs.ALLOCATED), set(rs.SUPPLIED), set(rs.LEFT_NULL)]
+    assert len(pointers) == 29 and sum(map(len, kinds)) == len(pointers)      # disjoint ...
+    assert set().union(*kinds) == pointers                                    # ... and complete
+    assert len(rs.SUPPLIED) == len(set(rs.SUPPLIED)) and len(rs.LEFT_NULL) == len(set(rs.LEFT_NULL))
+    for training in (False, True):
+        sizes = rs._Sizes(N=1, n_eval=2, n_final=1, n_extra=0, K=1, training=training, want_points=True)
+        assert sizes.S == 3
+        for name, (shape, dtype) in rs.ALLOCATED.items():
+            shape = shape(sizes)
+            assert len(shape) >= 1 and all(type(n) is int and n > 0 for n in shape), (name, shape)
+            assert dtype in (torch.float32, torch.int32), name
+    # the extents themselves, at sizes that tell their factors apart (S = 3 + 2 + 2)
+    shapes = {k: s(rs._Sizes(5, 7, 3, 2, 4, True, True)) for k, (s, _) in rs.ALLOCATED.items()}
+    assert shapes == {'z': (5, 28), 'sdf': (5, 28), 'new_z': (5, 7), 'new_pos': (5, 7), 'pts': (35, 3), 'beta': (5,),
+                      'flags': (8,), 'final_z': (5, 3), 'z_out': (5, 7), 'z_eik': (5, 1), 'pts_out': (55, 3),
+                      'far_out': (5, 1)}
+    assert rs.ALLOCATED['pts_out'][0](rs._Sizes(5, 7, 3, 2, 4, False, True)) == (35, 3)
+    assert rs.ALLOCATED['pts_out'][0](rs._Sizes(5, 7, 3, 2, 4, True, False)) is None
+
+
 def test_wgrad_schedule_rules_match_header():
     """plan.item_class / split_range / STAGE_POINTS and the class table against the C statement of the same rules in
     monosdf_plan.h (what the kernels dispatch on), for every item shape and the split counts listed below."""
