@@ -91,7 +91,30 @@ int msdf_abi_version(void);
  * skips that output (calc_grad_inputs == 0 skips grad_inputs), and with it the workspace is not looked at.  The table
  * gradient needs grad, inputs, offsets (and grad_grad_inputs, second order); grad_inputs needs grad and dy_dx;
  * grad_grad needs grad_grad_inputs and dy_dx.  node_scatter needs its three operands, inputs and offsets.
- * `embeddings` is never read.  MSDF_ERR_LAUNCH: the runtime refused a launch. */
+ * `embeddings` is never read.  MSDF_ERR_LAUNCH: the runtime refused a launch.
+ *
+ * Return codes of the entry points that read the table or its Jacobian -- msdf_hash_encode_forward, the grad_inputs
+ * part of msdf_hash_encode_backward and the grad_grad part of msdf_hash_encode_second_backward (grad_embeddings /
+ * grad2_embeddings NULL), msdf_hash_node_forward, msdf_hash_node_input_gradient, msdf_hash_node_second_grad,
+ * msdf_hash_transpose.  Again in this order, the first that fails decides, and a refused call launches nothing: the
+ * outputs are left untouched.
+ *
+ *   1  D != 3 (entries that take D); _backward and _second_backward:
+ *      their row 2 above as well, before B is looked at                      MSDF_ERR_UNSUPPORTED
+ *   2  B == 0: nothing is read, every pointer may be NULL -- also with a
+ *      C, pitch, n_split or L*C that rows 3 to 5 would refuse                MSDF_OK
+ *   3  a NULL required operand (below); pitch != 0 and pitch < L*C (node
+ *      forms; transpose: pitch < L*C, pitch 0 included); n_split > B
+ *      (node_second_grad); transpose: L*C == 0, or only one of src2 / dst2   MSDF_ERR_ARG
+ *   4  node_input_gradient: 3*B >= 2^32;
+ *      transpose: an LDS tile 64*(L*C + 1)*4 bytes > 64 KiB (L*C > 255)      MSDF_ERR_UNSUPPORTED
+ *   5  C not 1, 2, 4 or 8 (all but transpose, which takes any C)             MSDF_ERR_UNSUPPORTED
+ *
+ * Required operands.  _forward: inputs, embeddings, offsets, outputs, and dy_dx unless calc_grad_inputs == 0 (then
+ * dy_dx is neither read nor written).  _backward with calc_grad_inputs != 0: grad, dy_dx, grad_inputs;
+ * _second_backward with grad_grad given: grad_grad_inputs, dy_dx.  node_forward: x, embeddings, offsets, feat
+ * (x01_out and dy_dx may be NULL: not written).  node_input_gradient: g, dy_dx, inout.  node_second_grad: gg_out,
+ * dy_dx, grad_grad (g_a and g_b may each be NULL: that part of gg_out is zero).  transpose: src, dst. */
 int msdf_hash_encode_forward(const float* inputs, const float* embeddings, const int* offsets, float* outputs,
                              uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                              int calc_grad_inputs, float* dy_dx, void* stream);

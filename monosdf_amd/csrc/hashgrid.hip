@@ -350,7 +350,8 @@ hg_second_backward_grad_kernel(const float* __restrict__ gg_inputs, const float*
 
 // ---------------------------------------------------------------------------
 // C-ABI (mirrors hash_encode_forward / _backward / _second_backward of
-// code/hashencoder/src/hashencoder.h:13-15, same argument order, raw device pointers)
+// code/hashencoder/src/hashencoder.h:13-15, same argument order, raw device pointers).  Return codes of the entry
+// points that read the table or its Jacobian: the second table of the hash-grid block of include/monosdf_hip.h.
 // ---------------------------------------------------------------------------
 #define HG_DISPATCH_C(C, ...)                                    \
   switch (C) {                                                   \
@@ -366,6 +367,9 @@ extern "C" int msdf_hash_encode_forward(const float* inputs, const float* embedd
                                         uint32_t H, int calc_grad_inputs, float* dy_dx, void* stream) {
   if (D != 3) return MSDF_ERR_UNSUPPORTED;   // the reference also accepts D=2; this path only uses 3
   if (B == 0) return MSDF_OK;
+  if (inputs == nullptr || embeddings == nullptr || offsets == nullptr || outputs == nullptr ||
+      (calc_grad_inputs && dy_dx == nullptr))
+    return MSDF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((B + HG_THREADS - 1) / HG_THREADS, L);
   HG_DISPATCH_C(C, (hg_forward_kernel<CC><<<grid, HG_THREADS, 0, st>>>(inputs, embeddings, offsets, outputs, B, L, S,
@@ -565,7 +569,8 @@ extern "C" int msdf_hash_node_forward(const float* x, double divide_factor, floa
                                       const int* offsets, float* feat, uint32_t pitch, uint32_t B, uint32_t C,
                                       uint32_t L, float S, uint32_t H, float* dy_dx, void* stream) {
   if (B == 0) return MSDF_OK;          // as msdf_hash_encode_forward: nothing to do, NULL tensors allowed
-  if ((pitch != 0 && pitch < L * C) || x == nullptr || feat == nullptr) return MSDF_ERR_ARG;
+  if ((pitch != 0 && pitch < L * C) || x == nullptr || feat == nullptr || embeddings == nullptr || offsets == nullptr)
+    return MSDF_ERR_ARG;
   // what the module's `x / divide_factor` multiplies by on the device: the reciprocal formed in double, rounded to
   // fp32 (scripts/dbg/x01_rounding.py: bit-identical on 196,608 values; 1.0f / 1.1f differs in 41 % of them)
   const float inv = (float)(1.0 / divide_factor);

@@ -8,8 +8,10 @@ Both networks are built as integer ReLU networks:
            integer inputs: every hidden pre-activation is an integer = 2 (mod 4), so |a| >= 2 and softplus(beta = 100) IS
            ReLU (common.h: softplus100 returns a for a >= 2 and fma(0.01, 0, 0) = 0 for a <= -2; the sigmoid factor of the
            sweeps is exactly 0 or 1 and the second-order term exactly 0)
-  grid     the same SDF network behind a hash grid of four dense levels of scale 8, points on multiples of 1/8, integer
-           tables, first-layer weights multiples of 32: features, Jacobian and chain factor are dyadic numbers (GRID)
+  grid     the same SDF network behind a hash grid of levels of scale 8, points on multiples of 1/8, integer tables,
+           first-layer weights multiples of 32: features, Jacobian and chain factor are dyadic numbers.  The geometry
+           (num_levels, level_dim, logmap) belongs to the case (case.args, grid_conf()): between them the cases take
+           every piece of the SDF kernels' level-major loads and every path a grid model can run (grid_structure())
 
 A float64 evaluation of such a network is the exact answer, and every fp32 result -- whatever the summation order, on the
 fp32 matrix instructions or as bf16 plane products accumulated in fp32 -- is bit-equal to it as long as every term of a
@@ -28,6 +30,8 @@ certificate()  the conditions above, checked on those operands (and on the hash 
                test asserts it before it looks at a GPU result
 emulate()      a product as a core forms it: planes, kept pairs, fp32 accumulation in a shuffled order
 structure()    which gemm_tiles / gemm_b16 specialisation each product takes, from the plans of monosdf_amd/plan.py
+grid_structure()  hash-grid cases: the pieces of aux_load_tile / aux_store_tile (sdf_kernels.h) a case takes and which of
+               the five paths of a grid model a (core, flags) pair runs it on
 """
 import collections
 
@@ -126,25 +130,39 @@ def sdf_case(name, width=64, hidden=2, F=16, P=64, seed=0):
     return Case(name, 'sdf', dict(width=width, hidden=hidden, F=F, P=P), state, inputs, up)
 
 
-# Hash-grid model: four levels of scale 8 (S = 0, resolution 9, dense tables), points at multiples of 1/8 so that
-# x01 = k / 16 sits on a grid node or half-way between two (smoothstep 0, 1/2, 1: corner weights multiples of 1/8),
-# integer tables, first-layer weights multiples of 32 -- features, their Jacobian and the chain factor 0.5 are dyadic
-# numbers and the first pre-activation stays an integer = 2 (mod 4)
-GRID = dict(num_levels=4, level_dim=2, base_size=9, end_size=9, logmap=19, divide_factor=1.0)
+# Hash-grid model: levels of scale 8 (S = 0, resolution 9; dense tables of 729 entries, or hashed ones of 2^logmap
+# where that is smaller), points at multiples of 1/8 so that x01 = k / 16 sits on a grid node or half-way between two
+# (smoothstep 0, 1/2, 1: corner weights multiples of 1/8), integer tables, first-layer weights multiples of 32 --
+# features, their Jacobian and the chain factor 0.5 are dyadic numbers and the first pre-activation stays an integer
+# = 2 (mod 4).  What every grid case shares; num_levels, level_dim and logmap are in case.args
+GRID_FIXED = dict(base_size=9, end_size=9, divide_factor=1.0)
+# the geometry of the three first grid cases (grid_case's defaults): four dense levels of two features
+GRID = dict(GRID_FIXED, num_levels=4, level_dim=2, logmap=19)
 
 
-def grid_case(name, width=64, hidden=2, F=16, P=64, seed=0):
+def grid_conf(case):
+    """The hash-grid options of ImplicitNetworkGrid for this case (also what hg.level_geometry reads)."""
+    a = case.args
+    return dict(GRID_FIXED, num_levels=a['num_levels'], level_dim=a['level_dim'], logmap=a['logmap'])
+
+
+def grid_case(name, width=64, hidden=2, F=16, P=64, seed=0, num_levels=GRID['num_levels'], level_dim=GRID['level_dim'],
+              logmap=GRID['logmap']):
     """ImplicitNetworkGrid(F, 0.0, 3, 1, [width] * hidden, geometric_init = False, skip_in = (), weight_norm = False,
-    multires = 0, **GRID)."""
+    multires = 0, **grid_conf(case)).  level_dim = 1 has no second-order term (neither has the reference: no C = 1
+    second backward): its upstream gradient of d sdf / d x is zero and args['second_order'] False."""
     g = _gen(seed)
-    geo = hg.level_geometry(GRID)
-    n_aux = GRID['num_levels'] * GRID['level_dim']
+    args = dict(width=width, hidden=hidden, F=F, P=P, num_levels=num_levels, level_dim=level_dim, logmap=logmap,
+                second_order=level_dim > 1)
+    geo = hg.level_geometry(dict(GRID_FIXED, num_levels=num_levels, level_dim=level_dim, logmap=logmap))
+    n_aux = num_levels * level_dim
     base = sdf_case(name, width, hidden, F, P, seed + 1000)
     state = dict(base.state)
     state['lin0.weight'] = torch.cat([_sparse(g, width, 3, 1, (-32, 32)), _sparse(g, width, n_aux, 2, (-32, 32))], 1)
-    state['encoding.embeddings'] = _ints(g, (geo['n_entries'], GRID['level_dim']), -2, 2)
+    state['encoding.embeddings'] = _ints(g, (geo['n_entries'], level_dim), -2, 2)
     inputs = dict(x=_ints(g, (P, 3), -8, 8) / 8)
-    return Case(name, 'grid', dict(width=width, hidden=hidden, F=F, P=P), state, inputs, base.up)
+    up = base.up if level_dim > 1 else dict(base.up, C=torch.zeros_like(base.up['C']))
+    return Case(name, 'grid', args, state, inputs, up)
 
 
 def _cases(builder, specs):
@@ -200,6 +218,23 @@ GRID_CASES = _cases(grid_case, [
     ('w48_h3_p65', dict(width=48, hidden=3, P=65)),
     ('w64_h2_p17', dict(width=64, hidden=2, P=17)),
 ])
+# every aux layout and every path: (level_dim, num_levels, logmap) at P = 17 and 65 (and the reference's own 16 x 2 at
+# P = 213).  logmap 9: levels of 512 entries, hashed with a power-of-two size -- corners collide in the table gradient
+GRID_LAYOUTS = [(2, 3, 19), (2, 5, 19), (2, 8, 19), (2, 9, 19), (2, 15, 19), (2, 16, 19), (2, 4, 9),
+                (4, 3, 19), (4, 8, 19), (8, 2, 19), (8, 4, 19), (1, 5, 19)]
+
+
+def grid_layout_name(level_dim, num_levels, logmap, P):
+    return 'l%dc%d%s_p%d' % (num_levels, level_dim, '' if logmap == 19 else '_log%d' % logmap, P)
+
+
+GRID_LAYOUT_CASES = collections.OrderedDict()
+for _i, (_c, _l, _m) in enumerate(GRID_LAYOUTS):
+    for _j, _p in enumerate((17, 65, 213) if (_c, _l) == (2, 16) else (17, 65)):
+        _n = grid_layout_name(_c, _l, _m, _p)
+        GRID_LAYOUT_CASES[_n] = grid_case(_n, width=64, hidden=2, P=_p, seed=200 + 3 * _i + _j, num_levels=_l,
+                                          level_dim=_c, logmap=_m)
+GRID_CASES.update(GRID_LAYOUT_CASES)
 ALL_CASES = collections.OrderedDict()
 for _group, _cs in (('color', COLOR_CASES), ('sdf', SDF_CASES), ('probe', PROBE_CASES), ('grid', GRID_CASES)):
     for _n, _c in _cs.items():
@@ -247,7 +282,8 @@ def _reference_sdf(case):
     n = _n_layers(case)
     h = x
     if case.kind == 'grid':
-        feat = hg.hash_encode_autograd(x / GRID['divide_factor'], st['encoding.embeddings'], hg.level_geometry(GRID))
+        conf = grid_conf(case)
+        feat = hg.hash_encode_autograd(x / conf['divide_factor'], st['encoding.embeddings'], hg.level_geometry(conf))
         h = torch.cat([x, feat], 1)
     for l in range(n - 1):
         h = torch.relu(h @ st['lin%d.weight' % l].t() + st['lin%d.bias' % l])
@@ -344,8 +380,9 @@ def _color_products(case):
 
 def _grid_terms(case):
     """Hash-grid cases: x01, the features [n_aux, P] and the Jacobian J [P, L, 3, C] = d feature / d x01, in float64."""
-    geo = hg.level_geometry(GRID)
-    x01 = (case.inputs['x'].double() / GRID['divide_factor'] + 1) / 2
+    conf = grid_conf(case)
+    geo = hg.level_geometry(conf)
+    x01 = (case.inputs['x'].double() / conf['divide_factor'] + 1) / 2
     out, dy = hg.encode_forward(x01, case.state['encoding.embeddings'].double(), geo, True)
     P = x01.shape[0]
     return geo, x01, out.permute(1, 0, 2).reshape(P, -1).t(), dy.reshape(P, geo['L'], 3, geo['C'])
@@ -391,7 +428,7 @@ def _sdf_products(case):
     sums = []
     if grid:
         geo, x01, aux, J = _grid_terms(case)
-        k = 0.5 / GRID['divide_factor']                    # d x01 / d x
+        k = 0.5 / GRID_FIXED['divide_factor']              # d x01 / d x
         emb = case.state['encoding.embeddings'].double()
         sums.append(('grid.features', hg.encode_forward(x01, emb.abs(), geo, False)[0], 1 / 8 * granule(emb)))
     pr, pre, h = [], [], [torch.cat([x, aux], 0) if grid else x]
@@ -649,7 +686,7 @@ def build_plan(case):
     shapes = [tuple(case.state['lin%d.weight' % l].shape) for l in range(n)]
     if case.kind == 'color':
         return planlib.build_color_plan(shapes, a['mode'], 0, a['F'], 32 if a['code'] else 0, True)
-    n_aux = GRID['num_levels'] * GRID['level_dim'] if case.kind == 'grid' else 0
+    n_aux = a['num_levels'] * a['level_dim'] if case.kind == 'grid' else 0
     return planlib.build_sdf_plan(shapes, (), 0, n_aux, n_aux > 0, a['F'])
 
 
@@ -734,6 +771,109 @@ REACHES = {
 }
 
 
+# ---------------------------------------------------------------------------
+# hash-grid cases: the aux layouts of the SDF kernels and the paths of a grid model
+# ---------------------------------------------------------------------------
+# The five ways ImplicitNetworkGrid runs (model/network.py _SdfBase.evaluate, ops.GridSdfFunction, ops._encode_points),
+# and for each the hash-grid entry points one evaluation with its double backward must and must not call:
+#   fused_jacobian   fp32 core, two features per level: the SDF kernels read the encoder's level-major tensors and apply
+#                    its Jacobian themselves (aux_load_tile<true>, aux_store_tile<true>, aux_jacobian_transpose / _tile)
+#   level_major      the same without ops.FUSE_JACOBIAN: the Jacobian by the two small node kernels, pitch 0
+#   rows_fp32        fp32 core, level_dim 4 or 8: rows through msdf_hash_transpose, the node kernels at the row pitch
+#   rows_b16         the bf16 cores: rows, whatever the level_dim
+#   separate         ops.HASH_SCATTER == 'atomic', or level_dim 1: HashEncodeWithJacobian and HashEncodeBackwardFunction
+#                    around SdfMlpFunction, rows padded to whole tiles by the module
+_NODE = ('msdf_hash_node_forward', 'msdf_hash_node_scatter')
+_SMALL = ('msdf_hash_node_input_gradient', 'msdf_hash_node_second_grad')
+_REF_ORDER = ('msdf_hash_encode_forward', 'msdf_hash_encode_backward', 'msdf_hash_encode_second_backward')
+PATH_CALLS = {
+    'fused_jacobian': (_NODE, _SMALL + ('msdf_hash_transpose',) + _REF_ORDER),
+    'level_major': (_NODE + _SMALL, ('msdf_hash_transpose',) + _REF_ORDER),
+    'rows_fp32': (_NODE + _SMALL + ('msdf_hash_transpose',), _REF_ORDER),
+    'rows_b16': (_NODE + _SMALL + ('msdf_hash_transpose',), _REF_ORDER),
+    'separate': (_REF_ORDER, ('msdf_hash_node_scatter', 'msdf_hash_transpose') + _SMALL),
+}
+# the runs of tests/test_gpu_mlp_exact.py: name -> (core, ops.FUSE_JACOBIAN, ops.HASH_SCATTER)
+GRID_RUNS = collections.OrderedDict([
+    ('fp32', ('fp32', True, 'binned')), ('fp32_unfused', ('fp32', False, 'binned')),
+    ('fp32_atomic', ('fp32', True, 'atomic')), ('bf16x6', ('bf16x6', True, 'binned')),
+    ('bf16x3', ('bf16x3', True, 'binned'))])
+
+
+def grid_path(case, core, fuse_jacobian=True, hash_scatter='binned'):
+    """Which of the five paths this case takes on this core with these flags of monosdf_amd.ops."""
+    C = case.args['level_dim']
+    if hash_scatter == 'atomic' or C == 1:
+        return 'separate'
+    if core == 'fp32' and C == 2:
+        return 'fused_jacobian' if fuse_jacobian else 'level_major'
+    return 'rows_fp32' if core == 'fp32' else 'rows_b16'
+
+
+def grid_structure(case):
+    """aux_tiles of the plan, L C, and the pieces the lanes of a point take in aux_load_tile / aux_store_tile when the
+    tensors are level-major (a lane owns the columns s0 .. s0 + 3, s0 = 16 t + 4 q, of tile t < aux_tiles: two levels
+    of two features): 'full' both levels inside, 'half' (s0 + 2 == L C: only when L is odd) the first one, 'empty'
+    neither; as [(t, q, piece)] and as counts; `second_tile`: a tile 1 exists."""
+    a = case.args
+    lc = a['num_levels'] * a['level_dim']
+    tiles = build_plan(case).plan.aux_tiles
+    pieces = []
+    for t in range(tiles):
+        for q in range(4):
+            s0 = 16 * t + 4 * q
+            pieces.append((t, q, 'empty' if s0 >= lc else 'half' if s0 + 2 >= lc else 'full'))
+    count = lambda kind, t=None: sum(1 for tt, _, k in pieces if k == kind and (t is None or tt == t))
+    half = [(t, q) for t, q, k in pieces if k == 'half']
+    return dict(LC=lc, aux_tiles=tiles, second_tile=tiles > 1, pieces=pieces, full=count('full'), half=count('half'),
+                empty=count('empty'), half_at=half[0] if half else None, row_pad=16 * tiles - lc,
+                hashed=a['logmap'] < 10, level_major=a['level_dim'] == 2)
+
+
+# (level_dim, num_levels, logmap) -> the fields of grid_structure() the layout is there for
+GRID_REACHES = {
+    (2, 3, 19): dict(aux_tiles=1, full=1, half=1, empty=2, half_at=(0, 1)),              # half-piece in tile 0
+    (2, 5, 19): dict(aux_tiles=1, full=2, half=1, empty=1, half_at=(0, 2)),              # half-piece at q = 2
+    (2, 8, 19): dict(aux_tiles=1, full=4, half=0, empty=0),                              # one full tile
+    (2, 9, 19): dict(aux_tiles=2, second_tile=True, full=4, half=1, empty=3, half_at=(1, 0)),
+    (2, 15, 19): dict(aux_tiles=2, second_tile=True, full=7, half=1, empty=0, half_at=(1, 3)),
+    (2, 16, 19): dict(aux_tiles=2, second_tile=True, full=8, half=0, empty=0),           # the reference's own shape
+    (2, 4, 9): dict(aux_tiles=1, full=2, half=0, empty=2, hashed=True),                  # colliding corners
+    (2, 4, 19): dict(aux_tiles=1, full=2, half=0, empty=2, hashed=False),                # the three first cases
+    (4, 3, 19): dict(aux_tiles=1, level_major=False, row_pad=4),
+    (4, 8, 19): dict(aux_tiles=2, level_major=False, row_pad=0),
+    (8, 2, 19): dict(aux_tiles=1, level_major=False, row_pad=0),
+    (8, 4, 19): dict(aux_tiles=2, level_major=False, row_pad=0),
+    (1, 5, 19): dict(aux_tiles=1, level_major=False, row_pad=11),                        # rows padded from an odd width
+}
+# ... and the path each run of GRID_RUNS must take, by level_dim
+GRID_PATHS = {
+    2: dict(fp32='fused_jacobian', fp32_unfused='level_major', fp32_atomic='separate', bf16x6='rows_b16', bf16x3='rows_b16'),
+    4: dict(fp32='rows_fp32', fp32_unfused='rows_fp32', fp32_atomic='separate', bf16x6='rows_b16', bf16x3='rows_b16'),
+    8: dict(fp32='rows_fp32', fp32_unfused='rows_fp32', fp32_atomic='separate', bf16x6='rows_b16', bf16x3='rows_b16'),
+    1: dict(fp32='separate', fp32_unfused='separate', fp32_atomic='separate', bf16x6='separate', bf16x3='separate'),
+}
+
+
+def assert_grid_reaches(name, run=None):
+    """The layout assertions of one grid case and, for a run of GRID_RUNS, the path it must take.  Returns the path."""
+    case = ALL_CASES[name]
+    a = case.args
+    gs = grid_structure(case)
+    fields = GRID_REACHES[(a['level_dim'], a['num_levels'], a['logmap'])]
+    got = {k: gs[k] for k in fields}
+    assert got == fields, (name, got, fields)
+    geo = hg.level_geometry(grid_conf(case))
+    sizes = {geo['offsets'][l + 1] - geo['offsets'][l] for l in range(geo['L'])}
+    assert sizes == ({2 ** a['logmap']} if gs['hashed'] else {729}), (name, sizes)
+    if run is None:
+        return None
+    core, fuse, scatter = GRID_RUNS[run]
+    path = grid_path(case, core, fuse, scatter)
+    assert path == GRID_PATHS[a['level_dim']][run], (name, run, path)
+    return path
+
+
 def assert_reaches(name, core):
     """The structure assertions of one case on one core (a GPU test runs them before it runs the case)."""
     st = structure(ALL_CASES[name], core)
@@ -741,6 +881,8 @@ def assert_reaches(name, core):
         if c == core:
             got = {k: st[product][k] for k in fields}
             assert got == fields, (name, core, product, got, fields)
+    if ALL_CASES[name].kind == 'grid':
+        assert_grid_reaches(name)
 
 
 def first_difference(got, want_):

@@ -7,7 +7,8 @@ and weight gradient is compared with torch.equal: a lost plane product, a wrong 
 gradient column far below the tensor's maximum all show, which the 1e-4 max-norm bar of the parity tests does not see.
 
 A case runs on a core only where its certificate holds (the bf16x3 core forms three of the nine plane products); the fp32
-and bf16x6 cores run every case, and test_every_core_runs_every_kind asserts what is left for bf16x3."""
+and bf16x6 cores run every case, and test_every_core_runs_every_kind asserts what is left for bf16x3.  The hash-grid
+cases run on every path a grid model can take (mlp_exact_cases.GRID_RUNS), bf16x3 among them: it is certified on all."""
 import pytest
 import torch
 
@@ -140,7 +141,7 @@ def test_sdf_network_exact(name, core):
 
 def _grid_net(case, core):
     from monosdf_amd.model.network import ImplicitNetworkGrid
-    a, g = case.args, mx.GRID
+    a, g = case.args, mx.grid_conf(case)
     net = ImplicitNetworkGrid(a['F'], 0.0, 3, 1, [a['width']] * a['hidden'], geometric_init=False, skip_in=(),
                               weight_norm=False, multires=0, base_size=g['base_size'], end_size=g['end_size'],
                               logmap=g['logmap'], num_levels=g['num_levels'], level_dim=g['level_dim'],
@@ -153,33 +154,66 @@ def _grid_net(case, core):
     return net
 
 
-@pytest.mark.parametrize('core', mx.CORES)
+def _entry_points(prof):
+    """The hash-grid entry points among the recorded calls, the binned forms under their plain names."""
+    return {n[:-3] if n.endswith('_ws') else n for n in prof if n.startswith('msdf_hash_')}
+
+
+@pytest.mark.parametrize('run', list(mx.GRID_RUNS))
 @pytest.mark.parametrize('name', list(mx.GRID_CASES))
-def test_hash_grid_model_exact(name, core):
-    """ImplicitNetworkGrid end to end -- encoder, network, the grid part of d sdf/dx, the double backward with the table
-    gradient -- on four dense levels of scale 8 with points on multiples of 1/8.  The fp32 core reads the encoder's
-    level-major tensors and applies its Jacobian inside the kernels; the bf16 cores read rows."""
+def test_hash_grid_model_exact(name, run, monkeypatch):
+    """ImplicitNetworkGrid end to end -- encoder, network, the grid part of d sdf/dx, the double backward with the whole
+    table gradient -- on levels of scale 8 with points on multiples of 1/8, in every aux layout (half, full and empty
+    pieces of the level-major loads, one and two tiles, rows padded from 5, 6, 10, 12, 18 and 30 columns, hashed levels
+    with colliding corners) and on every path: the fp32 core with the Jacobian inside the SDF kernels, with
+    ops.FUSE_JACOBIAN off, with ops.HASH_SCATTER = 'atomic' (separate autograd nodes), and rows on the bf16 cores; four
+    or eight features per level take rows on the fp32 core too, one feature per level the separate nodes.  All paths
+    compute the same exact numbers, so all must give the same bits; the entry points each run calls are checked against
+    the path it is meant to take."""
+    from monosdf_amd import _lib, ops
     name = 'grid.' + name
+    core, fuse, scatter = mx.GRID_RUNS[run]
     case, ok = _certified(name, core)
     assert ok, (name, core)
+    path = mx.assert_grid_reaches(name, run)
+    monkeypatch.setattr(ops, 'FUSE_JACOBIAN', fuse)
+    monkeypatch.setattr(ops, 'HASH_SCATTER', scatter)
+    prof = {}
+    monkeypatch.setattr(_lib, 'PROFILE', prof)
+    monkeypatch.setattr(_lib, 'PROFILE_NAMES', None)
+    what = '%s (%s)' % (core, path)
     net = _grid_net(case, core)
     ref = mx.reference(case)
     x = case.inputs['x'].cuda()
     out = net(x)
-    _same(name, core, 'forward().sdf', out['sdf'], ref['sdf'])
-    _same(name, core, 'forward().feature', out['feature'], ref['feat'])
-    _same(name, core, 'gradient_sdf()', net.gradient_sdf(x), ref['grad'])
+    _same(name, what, 'forward().sdf', out['sdf'], ref['sdf'])
+    _same(name, what, 'forward().feature', out['feature'], ref['feat'])
+    _same(name, what, 'gradient_sdf()', net.gradient_sdf(x), ref['grad'])
     with torch.no_grad():
-        _same(name, core, 'get_sdf_vals()', net.get_sdf_vals(x), ref['sdf'])
+        _same(name, what, 'get_sdf_vals()', net.get_sdf_vals(x), ref['sdf'])
+    prof.clear()
     sdf, feat, grad = net.get_outputs(x)
     for k, t in (('sdf', sdf), ('feat', feat), ('grad', grad)):
-        _same(name, core, k, t, ref[k])
+        _same(name, what, k, t, ref[k])
     up = {k: v.cuda() for k, v in case.up.items()}
-    ((up['a'] * sdf).sum() + (up['B'] * feat).sum() + (up['C'] * grad).sum()).backward()
+    loss = (up['a'] * sdf).sum() + (up['B'] * feat).sum()
+    if case.args['second_order']:
+        loss = loss + (up['C'] * grad).sum()
+    loss.backward()
     params = dict(net.named_parameters())
     assert set(params) == set(case.state)
     for k, p in params.items():
-        _same(name, core, k, p.grad, ref[k])
+        _same(name, what, k, p.grad, ref[k])
+    called = _entry_points(prof)
+    must, must_not = mx.PATH_CALLS[path]
+    if not case.args['second_order']:
+        must = tuple(n for n in must if n != 'msdf_hash_encode_second_backward')
+    assert set(must) <= called and not set(must_not) & called, (name, run, path, sorted(called))
+    if not case.args['second_order']:
+        # one feature per level has no second backward (the reference has none either): the library says so
+        sdf, feat, grad = net.get_outputs(x)
+        with pytest.raises(RuntimeError, match='unsupported'):
+            grad.sum().backward()
 
 
 def test_every_core_runs_every_kind():
@@ -192,3 +226,4 @@ def test_every_core_runs_every_kind():
     for kind in ('color.', 'sdf.', 'probe.', 'grid.'):
         assert any(n.startswith(kind) for n in ok3), kind
     assert {'probe.w2f1g1', 'probe.w1f2g1', 'probe.w1f1g2'} <= set(ok3)
+    assert {n for n in mx.ALL_CASES if n.startswith('grid.')} <= set(ok3)

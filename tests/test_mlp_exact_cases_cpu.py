@@ -49,14 +49,19 @@ def test_sdf_inputs_keep_softplus_at_relu(name):
     x = case.inputs['x']
     if case.kind == 'grid':
         # points on multiples of 1/8 inside [-1, 1], both kinds of position (on a node, half-way) and both ends; integer
-        # tables; first-layer weights multiples of 32; dense levels of scale 8
+        # tables; first-layer weights multiples of 32; levels of scale 8, dense or (logmap 9) hashed with 512 entries
         W0, emb = case.state['lin0.weight'], case.state['encoding.embeddings']
         assert torch.equal(W0 % 32, torch.zeros_like(W0)) and torch.equal(emb, emb.round())
         assert x.abs().max() <= 1 and ((8 * x) % 2 == 0).any() and ((8 * x) % 2 == 1).any()
         x = 8 * x
-        geo = mx.hg.level_geometry(mx.GRID)
+        conf = mx.grid_conf(case)
+        geo = mx.hg.level_geometry(conf)
+        assert (conf['base_size'], conf['end_size'], conf['divide_factor']) == (9, 9, 1.0)
+        assert (geo['L'], geo['C']) == (case.args['num_levels'], case.args['level_dim'])
         assert geo['S'] == 0.0 and all(mx.hg.level_scale(geo, l) == (8.0, 9) for l in range(geo['L']))
-        assert [geo['offsets'][l + 1] - geo['offsets'][l] for l in range(geo['L'])] == [729] * geo['L']
+        size = 729 if case.args['logmap'] == 19 else 2 ** case.args['logmap']
+        assert size <= 729 and [geo['offsets'][l + 1] - geo['offsets'][l] for l in range(geo['L'])] == [size] * geo['L']
+        assert emb.shape == (geo['n_entries'], geo['C']) and W0.shape[1] == 3 + geo['L'] * geo['C']
     assert torch.equal(x, x.round())
     pre = mx.products(case)[2]
     assert len(pre) == hid and not mx.check_preactivations(pre)
@@ -70,6 +75,69 @@ def test_color_cases_hold_relu_ties(name):
     pre = mx.products(mx.COLOR_CASES[name])[2]
     for a in pre:
         assert (a == 0).any() and (a > 0).any() and (a < 0).any()
+
+
+# ---- hash-grid cases: geometry, layouts and paths ---------------------------------------------------------------------
+def test_first_grid_cases_keep_their_geometry():
+    """The three cases from before the geometry moved into case.args: four dense levels of two features."""
+    for n in ('w64_h2_p213', 'w48_h3_p65', 'w64_h2_p17'):
+        a = mx.GRID_CASES[n].args
+        assert (a['num_levels'], a['level_dim'], a['logmap'], a['second_order']) == (4, 2, 19, True)
+        assert mx.GRID_CASES[n].state['encoding.embeddings'].shape == (4 * 729, 2)
+
+
+def test_grid_layout_cases_cover_the_table():
+    layouts = {(c.args['level_dim'], c.args['num_levels'], c.args['logmap']) for c in mx.GRID_CASES.values()}
+    assert layouts == set(mx.GRID_REACHES) and set(mx.GRID_LAYOUTS) | {(2, 4, 19)} == layouts
+    for c, l, m in mx.GRID_LAYOUTS:
+        ps = {P for P in (17, 65, 213) if mx.grid_layout_name(c, l, m, P) in mx.GRID_CASES}
+        assert ps == ({17, 65, 213} if (c, l) == (2, 16) else {17, 65}), (c, l, m)
+    # level_dim 1 alone has no second-order term
+    assert {n for n, c in mx.GRID_CASES.items() if not c.args['second_order']} == {'l5c1_p17', 'l5c1_p65'}
+    for n in ('l5c1_p17', 'l5c1_p65'):
+        assert not mx.GRID_CASES[n].up['C'].any() and mx.GRID_CASES[n].up['a'].any()
+
+
+@pytest.mark.parametrize('name', ['grid.' + n for n in mx.GRID_CASES])
+def test_grid_cases_reach_their_layout_and_paths(name):
+    case = mx.ALL_CASES[name]
+    paths = {run: mx.assert_grid_reaches(name, run) for run in mx.GRID_RUNS}
+    assert set(paths.values()) <= set(mx.PATH_CALLS)
+    gs = mx.grid_structure(case)
+    assert gs['full'] + gs['half'] + gs['empty'] == 4 * gs['aux_tiles'] and gs['aux_tiles'] == -(-gs['LC'] // 16)
+    assert (gs['half'] == 1) == (gs['level_major'] and case.args['num_levels'] % 2 == 1) or not gs['level_major']
+    if gs['hashed']:
+        # corners of different grid points share table entries: the table gradient sums colliding records
+        geo = mx.hg.level_geometry(mx.grid_conf(case))
+        p = torch.stack(torch.meshgrid(*[torch.arange(10)] * 3, indexing='ij'), -1).reshape(-1, 3)
+        idx = mx.hg.grid_index(p, geo['offsets'][1] - geo['offsets'][0], 9)
+        assert idx.unique().numel() < p.shape[0] and mx.hg.grid_index(p[:1], 729, 9).item() == 0
+
+
+def test_grid_cases_take_every_piece_and_every_path():
+    """Between them the level-major cases take a full, a half and an empty piece in tile 0 and in tile 1, the half-piece
+    at every quarter; and the runs of GRID_RUNS take all five paths."""
+    seen, halves, paths = set(), set(), set()
+    for name, case in mx.GRID_CASES.items():
+        gs = mx.grid_structure(case)
+        if gs['level_major']:
+            seen |= {(t, k) for t, _, k in gs['pieces']}
+            halves |= {q for _, q, k in gs['pieces'] if k == 'half'}
+        for run, (core, fuse, scatter) in mx.GRID_RUNS.items():
+            paths.add(mx.grid_path(case, core, fuse, scatter))
+    assert seen == {(t, k) for t in (0, 1) for k in ('full', 'half', 'empty')}
+    assert halves == {0, 1, 2, 3}
+    assert paths == set(mx.PATH_CALLS)
+
+
+def test_grid_path_follows_the_flags():
+    c2, c4, c1 = mx.GRID_CASES['l16c2_p17'], mx.GRID_CASES['l8c4_p17'], mx.GRID_CASES['l5c1_p17']
+    assert mx.grid_path(c2, 'fp32') == 'fused_jacobian' and mx.grid_path(c2, 'fp32', fuse_jacobian=False) == 'level_major'
+    assert mx.grid_path(c2, 'bf16x6', fuse_jacobian=False) == 'rows_b16' and mx.grid_path(c4, 'fp32') == 'rows_fp32'
+    assert mx.grid_path(c4, 'bf16x3') == 'rows_b16' and mx.grid_path(c4, 'fp32', hash_scatter='atomic') == 'separate'
+    assert mx.grid_path(c1, 'fp32') == 'separate' and mx.grid_path(c1, 'bf16x6') == 'separate'
+    for must, must_not in mx.PATH_CALLS.values():
+        assert not set(must) & set(must_not)
 
 
 # ---- the certificate ----------------------------------------------------------------------------------------------
