@@ -563,7 +563,9 @@ __device__ __forceinline__ void sdf_fwd_grad_body(const msdf_plan_t& plan, const
     if (sph < sdf) {
       is_clamped = true;
       sdf = sph;
-      const float inv = -a.sphere_scale / nx;
+      // a clamped point at the origin: d |x| / d x is taken as 0 there, as torch.minimum(sdf, scale * (r - x.norm()))
+      // gives it (-scale / 0 would make the normals 0 * -inf = NaN)
+      const float inv = nx > 0.f ? -a.sphere_scale / nx : 0.f;
       n0 = c.x0 * inv; n1 = c.x1 * inv; n2 = c.x2 * inv;
     }
   }

@@ -4,10 +4,17 @@ computable in fp32, on the CPU only.
 Both networks are built as integer ReLU networks:
 
   colour   if_hdr (ReLU output, backward mask y > 0), multires_view = 0, no weight norm: affine maps and ReLUs only
-  SDF      multires = 0, no skip, no weight norm, no sphere clamp; hidden weights multiples of 4, hidden biases = 2 (mod 4),
-           integer inputs: every hidden pre-activation is an integer = 2 (mod 4), so |a| >= 2 and softplus(beta = 100) IS
+  SDF      multires = 0, no weight norm (SDF_CASES: no skip, no sphere clamp); hidden weights multiples of 4, hidden
+           biases = 2 (mod 4), integer inputs: every hidden pre-activation is an integer = 2 (mod 4), so |a| >= 2 and softplus(beta = 100) IS
            ReLU (common.h: softplus100 returns a for a >= 2 and fma(0.01, 0, 0) = 0 for a <= -2; the sigmoid factor of the
            sweeps is exactly 0 or 1 and the second-order term exactly 0)
+  skip     the same with skip_in = (l,): layer l reads [h | x] / sqrt(2).  The kernels fold s32 = float32(1 / sqrt(2))
+           into the packed weights, float32(s32 * W); the stored weights are the fp32 values v with float32(s32 * v) = 4
+           and = 8 exactly (skip_magnitudes()), so the layer is an integer layer for the kernels.  The gradient of the
+           stored weights is float32(s32) * float32(G), G the exact integer gradient of the effective ones
+  clamp    the same with the bounding-sphere clamp: integer points, dyadic radius and scale; sqrt, subtract, divide and
+           multiply restated in numpy fp32, one rounding per operation (clamp_restatement()), no decision near a tie
+  group    the clamp case under evaluate(x, n_clamp, n_feat, split): all choices compute the same exact integers
   grid     the same SDF network behind a hash grid of levels of scale 8, points on multiples of 1/8, integer tables,
            first-layer weights multiples of 32: features, Jacobian and chain factor are dyadic numbers.  The geometry
            (num_levels, level_dim, logmap) belongs to the case (case.args, grid_conf()): between them the cases take
@@ -34,7 +41,9 @@ grid_structure()  hash-grid cases: the pieces of aux_load_tile / aux_store_tile 
                the five paths of a grid model a (core, flags) pair runs it on
 """
 import collections
+import math
 
+import numpy as np
 import torch
 
 from monosdf_amd import plan as planlib
@@ -61,6 +70,18 @@ Product = collections.namedtuple('Product', 'name role unit A B adds key')
 
 def _gen(seed):
     return torch.Generator().manual_seed(seed)
+
+
+def _memo(cache, case, fn):
+    """fn(case), computed once per Case (or Product) object: keyed by identity, kept alive by the entry."""
+    ent = cache.get(id(case))
+    if ent is None or ent[0] is not case:
+        ent = cache[id(case)] = (case, fn(case))
+    return ent[1]
+
+
+def _n_layers(case):
+    return case.args['hidden'] + 1
 
 
 def _ints(g, shape, lo, hi):
@@ -113,21 +134,220 @@ def color_case(name, width=64, hidden=1, mode='idr', code=False, F=32, spr=1, P=
 HIDDEN_BIAS = (-6, -2, 2, 6)
 
 
-def sdf_case(name, width=64, hidden=2, F=16, P=64, seed=0):
-    """ImplicitNetwork(F, 0.0, 3, 1, [width] * hidden, geometric_init = False, skip_in = (), weight_norm = False,
-    multires = 0): sdf_bounding_sphere = 0 switches the clamp off."""
-    g = _gen(seed)
+def skip_scale(shapes, skip_in, F):
+    """The factor of a skip layer as the kernels hold it: msdf_packrule_t.scale of the plan (plan.py: 1 / sqrt(2)).  The
+    rule's field is a C float, which reads back as a Python float holding that fp32 value: s32 = float32(1 / sqrt(2))."""
+    mp = planlib.build_sdf_plan(list(shapes), tuple(skip_in), 0, 0, False, F)
+    s = {float(mp.rules[l].scale) for l in skip_in}
+    assert len(s) == 1
+    s32 = s.pop()
+    assert isinstance(s32, float) and float(np.float32(s32)) == s32 == float(np.float32(1.0 / math.sqrt(2.0)))
+    return s32
+
+
+def skip_magnitudes(s32):
+    """The stored fp32 magnitudes v4, v8 with float32(s32 * v) exactly 4 and exactly 8: searched among the fp32
+    neighbours of 4 sqrt(2) and 8 sqrt(2), nearest first (none exists for 3 or 12)."""
+    s, out = np.float32(s32), []
+    for k in (4.0, 8.0):
+        v = np.float32(k * math.sqrt(2.0))
+        lo = hi = v
+        cands = [v]
+        for _ in range(8):
+            lo, hi = np.nextafter(lo, np.float32(0)), np.nextafter(hi, np.float32(np.inf))
+            cands += [lo, hi]
+        hits = [c for c in cands if np.float32(s * c) == np.float32(k)]
+        assert hits, k
+        assert float(np.float32(s * hits[0])) == k
+        out.append(float(hits[0]))
+    return tuple(out)
+
+
+# points of the clamp cases, in front of the random ones: the origin; axis points (power-of-two norm: exact under any
+# sqrt); integer norms 3, 7 and 5 with permutations and signs
+SPECIAL_POINTS = ((0, 0, 0), (1, 0, 0), (0, -2, 0), (0, 0, 4), (1, 2, 2), (-2, 1, 2), (2, -2, -1), (2, 3, 6), (-6, 2, 3),
+                  (0, 3, 4), (4, 0, -3), (-3, -4, 0))
+CLAMP_MARGIN = 2.0 ** -10
+
+
+def _sdf_build(name, g, width, hidden, F, P, skip_in, radius, sphere_scale, n_clamp, n_feat, split):
     bias = torch.tensor(HIDDEN_BIAS, dtype=torch.float32)
     state = {}
+    outs = [width - 3 if (l + 1) in skip_in else width for l in range(hidden)]
+    shapes = [(outs[l], 3 if l == 0 else width) for l in range(hidden)] + [(1 + F, width)]
+    if skip_in:
+        assert all(0 < l < hidden for l in skip_in)
+        v4, v8 = skip_magnitudes(skip_scale(shapes, skip_in, F))
     for l in range(hidden):
-        cols = 3 if l == 0 else width
-        state['lin%d.weight' % l] = _sparse(g, width, cols, 2, (-4, 4))
-        state['lin%d.bias' % l] = bias[torch.randint(4, (width,), generator=g)]
+        rows, cols = shapes[l]
+        if l in skip_in:
+            # [h | x]: +-v4, +-v8, for the kernels the integers +-4, +-8; two non-zeros per row in h, one in x
+            vals = (-v8, -v4, v4, v8)
+            state['lin%d.weight' % l] = torch.cat([_sparse(g, rows, cols - 3, 2, vals), _sparse(g, rows, 3, 1, vals)], 1)
+        else:
+            state['lin%d.weight' % l] = _sparse(g, rows, cols, 2, (-4, 4))
+        state['lin%d.bias' % l] = bias[torch.randint(4, (rows,), generator=g)]
     state['lin%d.weight' % hidden] = _sparse(g, 1 + F, width, 4, (-2, -1, 1, 2))
     state['lin%d.bias' % hidden] = _ints(g, (1 + F,), -2, 2)
-    inputs = dict(x=_ints(g, (P, 3), -3, 3))
+    x = _ints(g, (P, 3), -3, 3)
+    if radius > 0:
+        ns = len(SPECIAL_POINTS)
+        assert P > ns
+        x[:ns] = torch.tensor(SPECIAL_POINTS, dtype=torch.float32)
+        x[P - 1] = 0                          # the origin again, in the ragged last workgroup
     up = dict(a=_ints(g, (P, 1), -2, 2), B=_ints(g, (P, F), -2, 2), C=_ints(g, (P, 3), -2, 2))
-    return Case(name, 'sdf', dict(width=width, hidden=hidden, F=F, P=P), state, inputs, up)
+    if split is not None:
+        # the node's backward receives two tensors per output; evaluate() does not return sdf [split:], so no gradient
+        # of it exists: the second of the pair is None.  B stays [P, F]: the loss uses its first n_feat rows
+        up = dict(a=(up['a'][:split], None), B=up['B'], C=(up['C'][:split], up['C'][split:]))
+    args = dict(width=width, hidden=hidden, F=F, P=P)
+    if skip_in or radius > 0 or split is not None or n_clamp is not None or n_feat is not None:
+        args.update(skip_in=tuple(skip_in), radius=float(radius), sphere_scale=float(sphere_scale), n_clamp=n_clamp,
+                    n_feat=n_feat, split=split)
+    return Case(name, 'sdf', args, state, dict(x=x), up)
+
+
+def sdf_case(name, width=64, hidden=2, F=16, P=64, seed=0, skip_in=(), radius=0.0, sphere_scale=1.0, n_clamp=None,
+             n_feat=None, split=None):
+    """ImplicitNetwork(F, radius, 3, 1, [width] * hidden, geometric_init = False, skip_in, weight_norm = False,
+    multires = 0, sphere_scale): radius = sdf_bounding_sphere = 0 switches the clamp off.
+    skip_in = (l,): layer l - 1 has width - 3 outputs, layer l reads [h | x] / sqrt(2) -- its stored weights are the fp32
+    values that the folded factor turns into +-4 and +-8 exactly (skip_magnitudes()).
+    radius, sphere_scale (dyadic): the points begin with SPECIAL_POINTS and end with the origin; the seed moves on
+    (seed + 1009 k) until clamp_conditions() holds -- every kind of point present, no decision within CLAMP_MARGIN.
+    n_clamp, n_feat, split: the arguments of evaluate() (None: P, P and no split, what get_outputs() passes); with a
+    split, up['a'] and up['C'] are the pairs of tensors the node's backward receives."""
+    skip_in = tuple(skip_in)
+    for k in range(64 if radius > 0 or skip_in else 1):
+        case = _sdf_build(name, _gen(seed + 1009 * k), width, hidden, F, P, skip_in, radius, sphere_scale, n_clamp,
+                          n_feat, split)
+        why = (clamp_conditions(case) if radius > 0 else []) + (skip_conditions(case) if skip_in else [])
+        if not why:
+            return case
+    raise AssertionError('%s: no seed gives the case what it is there for: %r' % (name, why[:3]))
+
+
+def skip_conditions(case):
+    """Reasons why a skip case does NOT show its skip layer (empty: it does): d sdf / d input behind the skip layer's
+    hidden tiles must be non-zero at half the points at least (a deep sparse ReLU network can be dead at most)."""
+    whole, first = _sdf_products(case)[1]['grad'], _sdf_products(case, 'one_input_arrival')[1]['grad']
+    alive = int((whole != first).any(1).sum())
+    return [] if 2 * alive >= case.args['P'] else ['skip: the input gradient arrives behind the skip layer at %d points of %d'
+                                                    % (alive, case.args['P'])]
+
+
+def groups(case):
+    """(n_clamp, n_feat, split) of the evaluation of this case: evaluate()'s arguments."""
+    a = case.args
+    P = a['P']
+    nc, nf = a.get('n_clamp'), a.get('n_feat')
+    return (P if nc is None else nc, P if nf is None else nf, a.get('split'))
+
+
+def effective_weight(case, l):
+    """float64 weights of layer l as the kernels multiply by them: float32(s32 * W) for a skip layer (the pack folds the
+    factor in, one rounding), W itself otherwise."""
+    W = case.state['lin%d.weight' % l]
+    skip = case.args.get('skip_in', ())
+    if l not in skip:
+        return W.double()
+    n = _n_layers(case)
+    s32 = skip_scale([tuple(case.state['lin%d.weight' % i].shape) for i in range(n)], skip, case.args['F'])
+    return (torch.tensor(s32, dtype=torch.float32) * W).double()
+
+
+def scaled_gradient(case, G):
+    """Gradient of the stored weights of a skip layer from the exact gradient G of the effective ones: msdf_reduce_k
+    applies the factor to the finished sum, one rounding: float32(s32) * float32(G)."""
+    n = _n_layers(case)
+    s32 = skip_scale([tuple(case.state['lin%d.weight' % i].shape) for i in range(n)], case.args['skip_in'], case.args['F'])
+    return (torch.tensor(s32, dtype=torch.float32) * G.float()).double()
+
+
+Clamp = collections.namedtuple('Clamp', 'nx sph normals')
+_CLAMP = {}
+
+
+def clamp_restatement(case):
+    """The clamp's fp32 arithmetic (sdf_kernels.h), one rounding per operation, in numpy: nx = sqrtf(x0 x0 + x1 x1 +
+    x2 x2) (integers: the sum is exact however it is fused), sph = scale * (r - nx), inv = -scale / nx (0 at the
+    origin, as torch's minimum gives that point a zero gradient), normals x_i * inv.  float64 tensors of fp32 values."""
+    def run(case):
+        a = case.args
+        x = case.inputs['x'].numpy().astype(np.float32)
+        r, sc = np.float32(a['radius']), np.float32(a['sphere_scale'])
+        nx = np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1] + x[:, 2] * x[:, 2])
+        sph = sc * (r - nx)
+        with np.errstate(divide='ignore'):
+            inv = np.where(nx > 0, -sc / nx, np.float32(0))
+        nrm = x * inv[:, None]
+        assert nx.dtype == sph.dtype == nrm.dtype == np.float32
+        t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).double()
+        return Clamp(t(nx), t(sph), t(nrm))
+    return _memo(_CLAMP, case, run)
+
+
+def raw_sdf(case):
+    """The unclamped sdf [P] of a case in float64 (forward chain only)."""
+    n = _n_layers(case)
+    x = case.inputs['x'].double()
+    h = x
+    for l in range(n - 1):
+        if l in case.args.get('skip_in', ()):
+            h = torch.cat([h, x], 1)
+        h = torch.relu(h @ effective_weight(case, l).t() + case.state['lin%d.bias' % l].double())
+    return h @ case.state['lin%d.weight' % (n - 1)].double()[0] + case.state['lin%d.bias' % (n - 1)].double()[0]
+
+
+def clamp_categories(case):
+    """Boolean masks [P] of the kinds of point a clamp case must hold; `would` = sph < sdf, whatever n_clamp says."""
+    c = clamp_restatement(case)
+    sdf = raw_sdf(case)
+    inside = c.nx < case.args['radius']
+    would = c.sph < sdf
+    x = case.inputs['x']
+    axis = (x != 0).sum(1) == 1
+    return collections.OrderedDict([
+        ('inside_unclamped', inside & ~would), ('inside_clamped', inside & would), ('outside_clamped', ~inside & would),
+        ('outside_unclamped', ~inside & ~would & (c.sph < 0)), ('integer_norm', (c.nx == c.nx.round()) & (c.nx > 0) & ~axis),
+        ('power_of_two_norm', axis & (torch.frexp(c.nx)[0] == 0.5)), ('origin', c.nx == 0), ('would', would)])
+
+
+def clamp_conditions(case):
+    """Reasons why a clamp case does NOT hold what it is there for (empty: it does).  No decision hangs on a rounding:
+    |sdf - sph| >= CLAMP_MARGIN everywhere (the net's sdf is an integer, sph an fp32 value).  With n_clamp >= 64 every
+    kind of point sits among the first n_clamp (the special points are the first twelve; the four kinds that depend on
+    the network need some tens of random points to turn up); with 0 < n_clamp < 64 the special points do and both a
+    clamped and an unclamped point; an origin among them is clamped.  With n_clamp < P a point beyond would be clamped."""
+    n_clamp, _, _ = groups(case)
+    P = case.args['P']
+    c = clamp_restatement(case)
+    sdf = raw_sdf(case)
+    why = []
+    if not torch.equal(sdf, sdf.round()):
+        why.append('clamp: the sdf is no integer')
+    if (sdf - c.sph).abs().min().item() < CLAMP_MARGIN:
+        why.append('clamp: |sdf - sph| = %g' % (sdf - c.sph).abs().min().item())
+    cat = clamp_categories(case)
+    head = torch.arange(P) < n_clamp
+    if not cat['inside_unclamped'].any() or not cat['outside_unclamped'].any():
+        why.append('clamp: the network leaves no point unclamped')
+    if n_clamp >= 64:
+        need = [k for k in cat if k != 'would']
+    elif n_clamp > 0:
+        need = ['integer_norm', 'power_of_two_norm', 'origin']
+        if not (head & cat['would']).any() or not (head & ~cat['would']).any():
+            why.append('clamp: no clamped or no unclamped point among the first %d' % n_clamp)
+    else:
+        need = []
+    for k in need:
+        if not (head & cat[k]).any():
+            why.append('clamp: no %s point among the first %d' % (k, n_clamp))
+    if n_clamp > 0 and not (head & cat['origin'] & cat['would']).any():
+        why.append('clamp: the origin is not clamped')
+    if n_clamp < P and not (~head & ~(c.nx < case.args['radius']) & cat['would']).any():
+        why.append('clamp: no outside point beyond n_clamp that would be clamped')
+    return why
 
 
 # Hash-grid model: levels of scale 8 (S = 0, resolution 9; dense tables of 729 entries, or hashed ones of 2^logmap
@@ -244,10 +464,6 @@ for _group, _cs in (('color', COLOR_CASES), ('sdf', SDF_CASES), ('probe', PROBE_
 # ---------------------------------------------------------------------------
 # float64 reference (autograd)
 # ---------------------------------------------------------------------------
-def _n_layers(case):
-    return case.args['hidden'] + 1
-
-
 def _color_input(case, feat, nrm, emb):
     a, i = case.args, case.inputs
     ray = torch.arange(a['P']) // a['spr']
@@ -285,24 +501,63 @@ def _reference_sdf(case):
         conf = grid_conf(case)
         feat = hg.hash_encode_autograd(x / conf['divide_factor'], st['encoding.embeddings'], hg.level_geometry(conf))
         h = torch.cat([x, feat], 1)
+    a = case.args
+    skip = a.get('skip_in', ())
+    # a skip layer multiplies by its effective weights (the gradient of the stored ones: scaled_gradient())
+    eff = {l: effective_weight(case, l).requires_grad_() for l in skip}
     for l in range(n - 1):
-        h = torch.relu(h @ st['lin%d.weight' % l].t() + st['lin%d.bias' % l])
+        if l in skip:
+            h = torch.cat([h, x], 1)
+        h = torch.relu(h @ (eff[l] if l in skip else st['lin%d.weight' % l]).t() + st['lin%d.bias' % l])
     o = h @ st['lin%d.weight' % (n - 1)].t() + st['lin%d.bias' % (n - 1)]
-    sdf, feat = o[:, :1], o[:, 1:]
+    raw, feat = o[:, :1], o[:, 1:]
+    n_clamp, n_feat, _ = groups(case)
+    sdf = raw
+    if a.get('radius', 0.0) > 0:
+        sph = a['sphere_scale'] * (a['radius'] - x.norm(dim=1, keepdim=True))
+        sdf = torch.where((torch.arange(a['P']) < n_clamp)[:, None], torch.minimum(raw, sph), raw)
     grad, = torch.autograd.grad(sdf.sum(), x, create_graph=True)
-    up = {k: v.double() for k, v in case.up.items()}
-    loss = (up['a'] * sdf).sum() + (up['B'] * feat).sum() + (up['C'] * grad).sum()
-    out = {'sdf': sdf.detach(), 'feat': feat.detach(), 'grad': grad.detach()}
-    out.update(dict(zip(st, torch.autograd.grad(loss, list(st.values())))))
+    ua, uB, uC = upstream(case)
+    loss = (ua * sdf).sum() + (uB * feat).sum() + (uC * grad).sum()
+    out = {'sdf': sdf.detach(), 'feat': feat.detach()[:n_feat], 'grad': grad.detach()}
+    if a.get('radius', 0.0) > 0:
+        # the clamped entries as the kernels' fp32 arithmetic gives them; forward() and gradient_sdf() do not clamp
+        c = clamp_restatement(case)
+        cl = (torch.arange(a['P']) < n_clamp) & (c.sph < raw.detach()[:, 0])
+        out['sdf'] = torch.where(cl[:, None], c.sph[:, None], out['sdf'])
+        out['grad'] = torch.where(cl[:, None], c.normals, out['grad'])
+        out['sdf_raw'] = raw.detach()
+        out['grad_raw'] = torch.autograd.grad(raw.sum(), x, retain_graph=True)[0]
+    leaves = [eff[int(k[3:-7])] if k.endswith('.weight') and int(k[3:-7]) in skip else v for k, v in st.items()]
+    for k, g in zip(st, torch.autograd.grad(loss, leaves)):
+        out[k] = scaled_gradient(case, g) if k.endswith('.weight') and int(k[3:-7]) in skip else g
     return out
 
 
-def _memo(cache, case, fn):
-    """fn(case), computed once per Case (or Product) object: keyed by identity, kept alive by the entry."""
-    ent = cache.get(id(case))
-    if ent is None or ent[0] is not case:
-        ent = cache[id(case)] = (case, fn(case))
-    return ent[1]
+def upstream(case, mutate=None):
+    """The upstream gradients of a case as float64 tensors over all P points: a [P, 1], B [P, F] with the rows from
+    n_feat on zero, C [P, 3].  With a split, a and C are put together from the pairs of tensors the node's backward
+    receives (no tensor: zeros).  mutate: what a wrong kernel would do ('feat_row_n_feat', 'second_tensor_at_pt')."""
+    P = case.args['P']
+    _, n_feat, split = groups(case)
+    up = case.up
+    if split is None:
+        a, C = up['a'].double(), up['C'].double()
+    else:
+        a, C = torch.zeros(P, 1, dtype=torch.float64), torch.zeros(P, 3, dtype=torch.float64)
+        for full, (first, second) in ((a, up['a']), (C, up['C'])):
+            full[:split] = first.double()
+            if second is None:
+                continue
+            if mutate == 'second_tensor_at_pt':
+                # row p >= split reads row p of the second tensor instead of row p - split (past its end: nothing)
+                m = second.shape[0]
+                full[split:m] = second.double()[split:m]
+            else:
+                full[split:] = second.double()
+    B = up['B'].double().clone()
+    B[n_feat + (1 if mutate == 'feat_row_n_feat' else 0):] = 0
+    return a, B, C
 
 
 _REFERENCE = {}
@@ -415,16 +670,33 @@ def _level_major(rows, geo):
     return rows.t().reshape(-1, geo['L'], geo['C']).permute(1, 0, 2).contiguous()
 
 
-def _sdf_products(case):
-    """ImplicitNetwork and ImplicitNetworkGrid.  Besides the products: `sums`, the other fp32 sums of the hash-grid
-    model as (name, sum of the terms' magnitudes, granule)."""
+# What a wrong kernel (or launcher) would do to the skip layer, the clamp or the point groups: _sdf_products(case, m)
+# restates the pass with that mistake in it.  tests/test_mlp_exact_cases_cpu.py shows that each one changes an expected
+# value of a certified case, i.e. that the exact comparison on the GPU would see it
+MUTATIONS = ('one_input_arrival',           # d sdf / d input behind the skip layer's hidden tiles is not taken
+             'no_input_columns',            # the skip layer's weight-gradient item without its input-block part
+             'scale_twice', 'no_scale',     # 1 / sqrt(2) on the finished weight-gradient sum: twice, not at all
+             'clamp_all',                   # points beyond n_clamp are clamped too
+             'clamped_live',                # clamped points hand a and C on to the parameter gradients
+             'no_feat_grad_when_clamped',   # ... or lose their feature gradient as well
+             'feat_row_n_feat',             # row n_feat gets features (and their gradient)
+             'second_tensor_at_pt')         # the second gradient tensor read at c.pt instead of c.pt - n_split
+
+
+def _sdf_products(case, mutate=None):
+    """ImplicitNetwork and ImplicitNetworkGrid.  Besides the products: `sums`, the other fp32 sums of the pass as
+    (name, sum of the terms' magnitudes, granule).  mutate: one of MUTATIONS (the result is then not the case's)."""
+    assert mutate is None or mutate in MUTATIONS
     n, hid = _n_layers(case), case.args['hidden']
-    W = [case.state['lin%d.weight' % l].double() for l in range(n)]
+    skip = tuple(case.args.get('skip_in', ()))
+    W = [effective_weight(case, l) for l in range(n)]
     b = [case.state['lin%d.bias' % l].double()[:, None] for l in range(n)]
     P = case.args['P']
     x = case.inputs['x'].double().t()                      # [3, P]: columns are points, as in the kernels
-    up = {k: v.double().t() for k, v in case.up.items()}
+    n_clamp, n_feat, split = groups(case)
+    up = dict(zip('aBC', (t.t() for t in upstream(case, mutate))))
     grid = case.kind == 'grid'
+    assert not (grid and (skip or case.args.get('radius', 0.0) > 0))
     sums = []
     if grid:
         geo, x01, aux, J = _grid_terms(case)
@@ -433,9 +705,11 @@ def _sdf_products(case):
         sums.append(('grid.features', hg.encode_forward(x01, emb.abs(), geo, False)[0], 1 / 8 * granule(emb)))
     pr, pre, h = [], [], [torch.cat([x, aux], 0) if grid else x]
     # forward chain (all three kernels)
+    hin = []                                               # what layer l multiplies: h_{l-1}, behind a skip [h_{l-1} | x]
     for l in range(hid):
-        pr.append(Product('l%d.fwd' % l, 'forward', 'core', W[l], h[-1], (b[l],), (l, 'f')))
-        pre.append(W[l] @ h[-1] + b[l])
+        hin.append(torch.cat([h[-1], x], 0) if l in skip else h[-1])
+        pr.append(Product('l%d.fwd' % l, 'forward', 'core', W[l], hin[l], (b[l],), (l, 'f')))
+        pre.append(W[l] @ hin[l] + b[l])
         h.append(torch.relu(pre[-1]))
     s = [(p > 0).double() for p in pre]
     # output layer: a matrix product where features are wanted, the sdf row as a dot product otherwise
@@ -443,13 +717,35 @@ def _sdf_products(case):
     pr.append(Product('out.dot', 'dot', 'dot', W[hid][:1], h[-1], (b[hid][:1],), None))
     o = W[hid] @ h[-1] + b[hid]
     # gradient sweep: p_l = s_l g_{l+1}, g_l = W_l^T p_l
+    # behind a skip layer's hidden rows the product yields d sdf / d input: its first arrival (the second: layer 0)
     p = {hid - 1: s[hid - 1] * W[hid][:1].t()}
+    arrivals = []
     for l in range(hid - 1, -1, -1):
         pr.append(Product('l%d.sweep' % l, 'transposed', 'core', W[l].t(), p[l], (), (l, 't')))
         g = W[l].t() @ p[l]
+        if l in skip:
+            arrivals.append(g[h[l].shape[0]:])
+            g = g[:h[l].shape[0]]
         if l > 0:
             p[l - 1] = s[l - 1] * g
     grad = g[:3]
+    if arrivals:
+        sums.append(('input_gradient', sum(t.abs() for t in arrivals) + grad.abs(), 1.0))
+        if mutate != 'one_input_arrival':
+            grad = grad + sum(arrivals)
+    # the bounding-sphere clamp, per point among the first n_clamp; a clamped point hands on neither a nor C
+    raw, grad_raw = o[:1], grad
+    sdf_row = raw
+    clamped = torch.zeros(P, dtype=torch.bool)
+    if case.args.get('radius', 0.0) > 0:
+        c = clamp_restatement(case)
+        clamped = (torch.arange(P) < (P if mutate == 'clamp_all' else n_clamp)) & (c.sph < raw[0])
+        sdf_row = torch.where(clamped, c.sph, raw[0])[None]
+        grad = torch.where(clamped, c.normals.t(), grad)
+    live = torch.ones(P, dtype=torch.float64) if mutate == 'clamped_live' else (~clamped).double()
+    up['a'], up['C'] = up['a'] * live, up['C'] * live
+    if mutate == 'no_feat_grad_when_clamped':
+        up['B'] = up['B'] * live
     q0 = up['C']
     if grid:
         # d sdf / d x through the grid: k sum_{l,c} r[l,c] J[l,d,c] with r = d sdf / d features; the gradient arriving at
@@ -463,8 +759,11 @@ def _sdf_products(case):
         sums.append(('grid.jacobian', (gg[:, None, :, None] * J).abs().sum(2), granule(gg) * granule(J)))
         q0 = torch.cat([up['C'], rbar], 0)
     # double backward, sweep up: q-bar_0 = C, p-bar_l = W_l q-bar_l, q-bar_{l+1} = s_l p-bar_l
+    # (behind a skip the input block of q-bar is C again: the second load_rbar)
     q = [q0]
     for l in range(hid):
+        if l in skip:
+            q[l] = torch.cat([q[l], q0], 0)
         pr.append(Product('l%d.up' % l, 'forward', 'core', W[l], q[l], (), (l, 'f')))
         q.append(s[l] * (W[l] @ q[l]))
     # sweep down: a-bar of the output layer = [a | B], a-bar_l = s_l W_{l+1}^T a-bar_{l+1} (second-order term: zero)
@@ -473,10 +772,12 @@ def _sdf_products(case):
     ab[hid - 1] = s[hid - 1] * (W[hid].t() @ ab[hid])
     for l in range(hid - 1, 0, -1):
         pr.append(Product('l%d.down' % l, 'transposed', 'core', W[l].t(), ab[l], (), (l, 't')))
-        ab[l - 1] = s[l - 1] * (W[l].t() @ ab[l])
+        ab[l - 1] = s[l - 1] * (W[l].t() @ ab[l])[:h[l].shape[0]]      # (a skip layer's input rows: d loss / d x, unused)
     # weight gradients: d W_l = p_l q-bar_l^T + a-bar_l h_l^T, both terms reduced into one sum
     ones = torch.ones(P, 1, dtype=torch.float64)
-    out = {'sdf': o[:1].t(), 'feat': o[1:].t(), 'grad': grad.t()}
+    out = {'sdf': sdf_row.t(), 'feat': o[1:].t()[:n_feat], 'grad': grad.t()}
+    if case.args.get('radius', 0.0) > 0:
+        out['sdf_raw'], out['grad_raw'] = raw.t(), grad_raw.t()
     if grid:
         # the product down to the network input runs for its feature rows: d loss / d features; the table gradient is its
         # scatter plus the second-order term of the grid part of d sdf / d x
@@ -492,10 +793,24 @@ def _sdf_products(case):
                      _second_order_magnitude(r_lm, x01, gg, geo, n_e),
                      min(1 / 8 * granule(g_aux), granule(gg) * granule(r_lm))))
     for l in range(hid):
-        A, B = torch.cat([p[l], ab[l]], 1), torch.cat([q[l].t(), h[l].t()], 0)
-        pr.append(Product('l%d.wgrad' % l, 'wgrad', 'wgrad', A, B, (), None))
+        A, B = torch.cat([p[l], ab[l]], 1), torch.cat([q[l].t(), hin[l].t()], 0)
+        if l in skip:
+            # a two-part item (plan.py _col_parts): the hidden columns and the input block, each a product of its own;
+            # the reduction applies 1 / sqrt(2) to the finished sums
+            nh = h[l].shape[0]
+            pr.append(Product('l%d.wgrad' % l, 'wgrad', 'wgrad', A, B[:, :nh], (), None))
+            pr.append(Product('l%d.wgrad_in' % l, 'wgrad', 'wgrad', A, B[:, nh:], (), None))
+            G = A @ B
+            if mutate == 'no_input_columns':
+                G[:, nh:] = 0
+            sums.append(('l%d.scaled_gradient' % l, G.abs(), 1.0))
+            dW = G if mutate == 'no_scale' else scaled_gradient(case, G)
+            out['lin%d.weight' % l] = scaled_gradient(case, dW) if mutate == 'scale_twice' else dW
+        else:
+            pr.append(Product('l%d.wgrad' % l, 'wgrad', 'wgrad', A, B, (), None))
+            out['lin%d.weight' % l] = A @ B
         pr.append(Product('b%d.colsum' % l, 'dot', 'dot', ab[l], ones, (), None))
-        out['lin%d.weight' % l], out['lin%d.bias' % l] = A @ B, ab[l].sum(1)
+        out['lin%d.bias' % l] = ab[l].sum(1)
     pr.append(Product('out.wgrad', 'wgrad', 'wgrad', ab[hid][1:], h[hid].t(), (), None))
     # the sdf row: sum_p a[p] h[p] (the v-weighted row sums) + the column sums of the last q-bar, plain fp32
     A, B = torch.cat([up['a'], ones.t()], 1), torch.cat([h[hid].t(), q[hid].t()], 0)
@@ -503,8 +818,14 @@ def _sdf_products(case):
     pr.append(Product('b%d.colsum' % hid, 'dot', 'dot', ab[hid], ones, (), None))
     out['lin%d.weight' % hid] = torch.cat([A @ B, ab[hid][1:] @ h[hid].t()], 0)
     out['lin%d.bias' % hid] = ab[hid].sum(1)
-    _SUMS[id(case)] = (case, sums)
+    if mutate is None:
+        _SUMS[id(case)] = (case, sums)
     return pr, out, pre
+
+
+def mutated_outputs(case, mutate):
+    """The outputs of an SDF case as a kernel with the mistake `mutate` (MUTATIONS) would give them."""
+    return _sdf_products(case, mutate)[1]
 
 
 _SUMS = {}
@@ -632,6 +953,8 @@ def certificate(case, core):
             why += check_product(p, core)
         if case.kind != 'color':
             why += check_preactivations(pre)
+        if case.args.get('radius', 0.0) > 0:
+            why += clamp_conditions(case)
         for name, mag, g in other_sums(case):
             if mag.numel() and mag.max().item() >= SUM_BOUND * g:
                 why.append('%s: sum of magnitudes %g reaches 2^24 granules of %g' % (name, mag.max().item(), g))
@@ -687,7 +1010,7 @@ def build_plan(case):
     if case.kind == 'color':
         return planlib.build_color_plan(shapes, a['mode'], 0, a['F'], 32 if a['code'] else 0, True)
     n_aux = a['num_levels'] * a['level_dim'] if case.kind == 'grid' else 0
-    return planlib.build_sdf_plan(shapes, (), 0, n_aux, n_aux > 0, a['F'])
+    return planlib.build_sdf_plan(shapes, tuple(a.get('skip_in', ())), 0, n_aux, n_aux > 0, a['F'])
 
 
 def _describe(core, k, ot):
@@ -706,10 +1029,16 @@ def _describe(core, k, ot):
 
 
 def structure(case, core):
-    """{product name: what the matrix core dispatches on for it}, for the products a matrix core forms."""
+    """{product name: what the matrix core dispatches on for it}, for the products a matrix core forms -- and, for the
+    weight-gradient item of a skip layer (no 'kernel' field), its two column parts as (slot start, width), the tile the
+    input block sits at and the layer's kt."""
     mp = build_plan(case)
     plan = mp.plan if core == 'fp32' else mp.build_b16(PLANES[core])
     out = {}
+    for l in case.args.get('skip_in', ()) if case.kind == 'sdf' else ():
+        L = mp.plan.layer[l]
+        parts = planlib._col_parts(L, mp.in0_tiles)
+        out['l%d.wgrad' % l] = dict(two_part=len(parts) == 2, parts=parts, skip_tile=L.skip_tile, kt=L.kt)
     for pr in products(case)[0]:
         if pr.key is None:
             continue
@@ -768,7 +1097,36 @@ REACHES = {
     'sdf.w64_h2_p213': [
         ('fp32', 'l1.fwd', dict(kernel='gemm_tiles<0,1>', k=4)),
         ('bf16x3', 'l0.fwd', dict(kernel='gemm_b16<2,2>')), ('bf16x6', 'l1.fwd', dict(kernel='gemm_b16<3,2>'))],
+    # skip layers: the input block behind 4, 3, 7, 11 and 14 hidden tiles; the transposed product has kt out tiles
+    'skip.w64_h3_s2_p213': [
+        ('fp32', 'l2.fwd', dict(kernel='gemm_tiles<0,1>', k=7, out_tiles=4)),
+        ('fp32', 'l2.sweep', dict(k=4, out_tiles=7, odd_last_tile=True)),
+        ('bf16x3', 'l2.fwd', dict(kernel='gemm_b16<2,0>', k=4)), ('bf16x6', 'l2.down', dict(kernel='gemm_b16<3,2>', out_tiles=7)),
+    ] + [(c, 'l2.wgrad', dict(two_part=True, parts=[(0, 64), (64, 48)], skip_tile=4, kt=7)) for c in CORES],
+    'skip.w48_h2_s1_p65': [
+        ('fp32', 'l1.fwd', dict(kernel='gemm_tiles<0,1>', k=6, out_tiles=3)),
+        ('fp32', 'l1.sweep', dict(kernel='gemm_tiles<3,4>', out_tiles=6, chunks=1)),
+        ('bf16x3', 'l1.up', dict(kernel='gemm_b16<2,3>')), ('bf16x6', 'l1.fwd', dict(kernel='gemm_b16<3,3>')),
+    ] + [(c, 'l1.wgrad', dict(two_part=True, parts=[(0, 48), (48, 48)], skip_tile=3, kt=6)) for c in CORES],
+    'skip.w100_h3_s2_p63': [
+        ('fp32', 'l2.fwd', dict(kernel='gemm_tiles<0,1>', k=10, out_tiles=7)),
+        ('bf16x6', 'l2.fwd', dict(kernel='gemm_b16<3,0>', k=5)),
+    ] + [(c, 'l2.wgrad', dict(two_part=True, parts=[(0, 112), (112, 48)], skip_tile=7, kt=10)) for c in CORES],
+    # kt = 14 padded to the unrolled K = 16 path
+    'skip.w176_h4_s2_p17': [
+        ('fp32', 'l2.fwd', dict(kernel='gemm_tiles<16,1>', k=16, out_tiles=11)),
+        ('fp32', 'l2.sweep', dict(kernel='gemm_tiles<0,1>', k=11, out_tiles=14)),
+        ('bf16x3', 'l2.fwd', dict(kernel='gemm_b16<2,8>')),
+    ] + [(c, 'l2.wgrad', dict(two_part=True, parts=[(0, 176), (176, 48)], skip_tile=11, kt=14)) for c in CORES],
+    # kt = 17 = MT: the register layout's maximum, the tile count of the reference's headline network
+    'skip.w227_h3_s2_p65': [
+        ('fp32', 'l2.fwd', dict(kernel='gemm_tiles<17,1>', k=17, out_tiles=15)),
+        ('fp32', 'l2.sweep', dict(kernel='gemm_tiles<16,1>', out_tiles=17, dead_pair=True)),
+        ('bf16x3', 'l2.fwd', dict(kernel='gemm_b16<2,9>')), ('bf16x6', 'l2.up', dict(kernel='gemm_b16<3,9>')),
+    ] + [(c, 'l2.wgrad', dict(two_part=True, parts=[(0, 224), (224, 48)], skip_tile=14, kt=MT)) for c in CORES],
+    'clamp.w64_h3_s2_r2.5_p65': [(c, 'l2.wgrad', dict(two_part=True, skip_tile=4, kt=7)) for c in CORES],
 }
+REACHES['skip.w227_h3_s2_p1'] = REACHES['skip.w227_h3_s2_p65']
 
 
 # ---------------------------------------------------------------------------
@@ -900,3 +1258,37 @@ def first_difference(got, want_):
     r, c = int(ne[0, 0]), int(ne[0, 1])
     return dict(row=r, column=c, workgroup=r // 64, wave=r % 64 // 16, tile=c // 16, quarter=c % 16 // 4,
                 component=c % 4, got=float(g2[r, c]), want=float(w2[r, c]), n_different=int(ne.shape[0]))
+
+
+# ---------------------------------------------------------------------------
+# skip, clamp and group cases (built down here: their builder looks at the pass itself, skip_conditions())
+# ---------------------------------------------------------------------------
+# the skip layer (every MLP configuration of the reference has one): 61 outputs = four tiles with 13 live slots in the
+# last; right behind the input layer; 97 outputs, padded; 173 outputs with kt = 14 padded to the K = 16 path; 224
+# outputs = 14 tiles + 3 = kt 17 = MT, the register layout's maximum
+SDF_SKIP_CASES = _cases(sdf_case, [
+    ('w64_h3_s2_p213', dict(width=64, hidden=3, skip_in=(2,), P=213)),
+    ('w48_h2_s1_p65', dict(width=48, hidden=2, skip_in=(1,), P=65)),
+    ('w100_h3_s2_p63', dict(width=100, hidden=3, skip_in=(2,), P=63)),
+    ('w176_h4_s2_p17', dict(width=176, hidden=4, skip_in=(2,), P=17)),
+    ('w227_h3_s2_p1', dict(width=227, hidden=3, skip_in=(2,), P=1)),
+])
+SDF_SKIP_CASES.update((n, sdf_case(n, seed=110 + i, **kw)) for i, (n, kw) in enumerate([
+    ('w227_h3_s2_p65', dict(width=227, hidden=3, skip_in=(2,), P=65))]))
+# the bounding-sphere clamp on every point (get_outputs(), get_sdf_vals()): dyadic radius and scale
+SDF_CLAMP_CASES = collections.OrderedDict((n, sdf_case(n, seed=120 + i, **kw)) for i, (n, kw) in enumerate([
+    ('w64_h2_r2.5_p213', dict(width=64, hidden=2, radius=2.5, sphere_scale=1.0, P=213)),
+    ('w100_h2_r3_s0.5_p65', dict(width=100, hidden=2, radius=3.0, sphere_scale=0.5, P=65)),
+    ('w64_h3_s2_r2.5_p65', dict(width=64, hidden=3, skip_in=(2,), radius=2.5, sphere_scale=1.0, P=65)),
+]))
+# the point groups of one launch: three workgroups of 64, the last ragged; (n_clamp, n_feat, split)
+GROUPS = [(0, 0, 0), (17, 1, 15), (64, 16, 64), (150, 63, 129), (17, 64, 150), (64, 65, 15), (150, 150, 0),
+          (0, 150, 129), (17, 63, 64), (150, 65, 150)]
+SDF_GROUP_CASES = collections.OrderedDict()
+for _i, (_c, _f, _s) in enumerate(GROUPS):
+    _n = 'c%d_f%d_s%d' % (_c, _f, _s)
+    SDF_GROUP_CASES[_n] = sdf_case(_n, width=64, hidden=2, P=150, seed=130, radius=2.5, sphere_scale=1.0, n_clamp=_c,
+                                   n_feat=_f, split=_s)
+for _group, _cs in (('skip', SDF_SKIP_CASES), ('clamp', SDF_CLAMP_CASES), ('group', SDF_GROUP_CASES)):
+    for _n, _c in _cs.items():
+        ALL_CASES['%s.%s' % (_group, _n)] = _c

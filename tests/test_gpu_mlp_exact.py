@@ -94,8 +94,9 @@ def test_plane_probes(name, core):
 def _sdf_net(case, core):
     from monosdf_amd.model.network import ImplicitNetwork
     a = case.args
-    net = ImplicitNetwork(a['F'], 0.0, 3, 1, [a['width']] * a['hidden'], geometric_init=False, skip_in=(),
-                          weight_norm=False, multires=0)
+    net = ImplicitNetwork(a['F'], a.get('radius', 0.0), 3, 1, [a['width']] * a['hidden'], geometric_init=False,
+                          skip_in=a.get('skip_in', ()), weight_norm=False, multires=0,
+                          sphere_scale=a.get('sphere_scale', 1.0))
     net.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
     net = net.cuda()
     net.set_precision(core)
@@ -110,11 +111,15 @@ def _run_sdf(name, core):
     ref = mx.reference(case)
     x = case.inputs['x'].cuda()
     # forward(): the output layer as a matrix product; gradient_sdf(): the sdf row as a dot product, no features;
-    # get_sdf_vals() without autograd: the forward-only kernel
+    # get_sdf_vals() without autograd: the forward-only kernel.  The first two never clamp (sdf_raw, grad_raw of a clamp
+    # case); get_sdf_vals() clamps every point, through the forward + gradient kernel under autograd and through the
+    # forward-only kernel (fminf) without
     out = net(x)
-    _same(name, core, 'forward().sdf', out[:, :1], ref['sdf'])
+    _same(name, core, 'forward().sdf', out[:, :1], ref.get('sdf_raw', ref['sdf']))
     _same(name, core, 'forward().feat', out[:, 1:], ref['feat'])
-    _same(name, core, 'gradient_sdf()', net.gradient_sdf(x), ref['grad'])
+    _same(name, core, 'gradient_sdf()', net.gradient_sdf(x), ref.get('grad_raw', ref['grad']))
+    if 'sdf_raw' in ref:
+        _same(name, core, 'get_sdf_vals() under autograd', net.get_sdf_vals(x), ref['sdf'])
     with torch.no_grad():
         _same(name, core, 'get_sdf_vals()', net.get_sdf_vals(x), ref['sdf'])
     # all three outputs of one evaluation and the double backward to every parameter
@@ -128,6 +133,60 @@ def _run_sdf(name, core):
     for k, p in params.items():
         _same(name, core, k, p.grad, ref[k])
     return True
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.SDF_SKIP_CASES))
+def test_sdf_skip_exact(name, core):
+    """The skip layer: the input block behind 3, 4, 7, 11 and 14 hidden tiles (kt = 17, the register layout's maximum) in
+    all four kernel bodies, d sdf / d input arriving twice, the second load of C in the double backward, the two-part
+    weight-gradient item, and 1 / sqrt(2) folded into the pack and applied once more to the finished weight-gradient sum:
+    the stored weights are the fp32 values that the folded factor turns into +-4 and +-8 exactly, and the expected
+    gradient of the stored weights is float32(1 / sqrt(2)) * float32(exact integer gradient), one rounding."""
+    assert _run_sdf('skip.' + name, core)
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.SDF_CLAMP_CASES))
+def test_sdf_clamp_exact(name, core):
+    """The bounding-sphere clamp on integer points with dyadic radius and scale: the decision sph < sdf per point (never
+    within 2^-10 of a tie), the clamped sdf and the normal -scale x / |x| as numpy restates them in fp32, one rounding per
+    operation (points of integer and power-of-two norm among them; the origin, clamped, has sdf = scale r and normals
+    0), and parameter gradients to which clamped points hand on their feature gradient alone."""
+    assert _run_sdf('clamp.' + name, core)
+
+
+@pytest.mark.parametrize('core', mx.CORES)
+@pytest.mark.parametrize('name', list(mx.SDF_GROUP_CASES))
+def test_sdf_point_groups_exact(name, core):
+    """evaluate(x, n_clamp, n_feat, split = s) over three workgroups, the last ragged: the first n_clamp points clamped,
+    the first n_feat with features (the matrix-product output layer in their workgroups, the sdf row as a dot product in
+    the others), the upstream gradients of d sdf / d x from two tensors split at s -- at and off the multiples of 16 and
+    64.  Both forms of the output layer and both tensors carry the same exact integers, so every choice gives the bits
+    of the reference.  (evaluate() keeps the clamped flags to itself: they show in the gradients.)"""
+    name = 'group.' + name
+    case, ok = _certified(name, core)
+    assert ok, (name, core)
+    net = _sdf_net(case, core)
+    ref = mx.reference(case)
+    n_clamp, n_feat, s = mx.groups(case)
+    P = case.args['P']
+    sdf, feat, grad_a, grad_b = net.evaluate(case.inputs['x'].cuda(), n_clamp, n_feat, split=s)
+    assert sdf.shape == (s, 1) and feat.shape == (n_feat, case.args['F'])
+    assert grad_a.shape == (s, 3) and grad_b.shape == (P - s, 3)
+    _same(name, core, 'sdf', sdf, ref['sdf'][:s])
+    _same(name, core, 'feat', feat, ref['feat'])
+    _same(name, core, 'grad [:split]', grad_a, ref['grad'][:s])
+    _same(name, core, 'grad [split:]', grad_b, ref['grad'][s:])
+    (a, none), (C_a, C_b), B = case.up['a'], case.up['C'], case.up['B']
+    assert none is None
+    loss = (a.cuda() * sdf).sum() + (B[:n_feat].cuda() * feat).sum() + (C_a.cuda() * grad_a).sum() + \
+        (C_b.cuda() * grad_b).sum()
+    loss.backward()
+    params = dict(net.named_parameters())
+    assert set(params) == set(case.state)
+    for k, p in params.items():
+        _same(name, core, k, p.grad, ref[k])
 
 
 @pytest.mark.parametrize('core', mx.CORES)
@@ -223,7 +282,7 @@ def test_every_core_runs_every_kind():
         bad = [n for n, c in mx.ALL_CASES.items() if not mx.certificate(c, core).ok]
         assert not bad, (core, bad)
     ok3 = [n for n, c in mx.ALL_CASES.items() if mx.certificate(c, 'bf16x3').ok]
-    for kind in ('color.', 'sdf.', 'probe.', 'grid.'):
+    for kind in ('color.', 'sdf.', 'probe.', 'grid.', 'skip.', 'clamp.', 'group.'):
         assert any(n.startswith(kind) for n in ok3), kind
     assert {'probe.w2f1g1', 'probe.w1f2g1', 'probe.w1f1g2'} <= set(ok3)
     assert {n for n in mx.ALL_CASES if n.startswith('grid.')} <= set(ok3)

@@ -152,7 +152,7 @@ def test_certificate_accepts_the_cases(name):
 
 def test_every_core_has_a_full_case_of_every_kind():
     ok3 = [n for n in NAMES if mx.certificate(mx.ALL_CASES[n], 'bf16x3').ok]
-    for kind in ('color.', 'sdf.', 'probe.', 'grid.'):
+    for kind in ('color.', 'sdf.', 'probe.', 'grid.', 'skip.', 'clamp.', 'group.'):
         assert any(n.startswith(kind) for n in ok3)
     # a full case: forward, transposed and weight-gradient products, all of them certified
     for n in ('color.w100_h2_idr_code_f40_p63', 'sdf.w48_h3_f24_p65'):
@@ -326,6 +326,8 @@ def test_cases_reach_the_branches_they_are_named_for(core):
     kernels, flags = set(), set()
     for name, case in mx.ALL_CASES.items():
         for d in mx.structure(case, core).values():
+            if 'kernel' not in d:               # the two-part weight-gradient item of a skip layer: no matrix-core product
+                continue
             kernels.add(d['kernel'])
             flags |= {k for k in ('odd_last_tile', 'dead_pair', 'partial_last_chunk') if d[k]}
             if core == 'fp32' and d['pairs_per_chunk'] > 1:
@@ -362,3 +364,247 @@ def test_first_difference_names_the_slot():
     assert d['n_different'] == 2 and d['got'] == 1.0 and d['want'] == 0.0
     assert mx.first_difference(torch.zeros(3), torch.zeros(4)) == dict(shape=((3,), (4,)))
     assert mx.first_difference(torch.tensor([0.0, 2.0]), torch.tensor([0.0, 1.0]))['row'] == 1
+
+
+# ---- the skip layer, the sphere clamp and the point groups ----------------------------------------------------------
+NEW_SDF = ['skip.' + n for n in mx.SDF_SKIP_CASES] + ['clamp.' + n for n in mx.SDF_CLAMP_CASES] + \
+    ['group.' + n for n in mx.SDF_GROUP_CASES]
+
+
+def test_new_sdf_cases_are_certified_on_all_three_cores():
+    """Skip, clamp and group cases hold their certificates on fp32, bf16x6 and -- every one of them -- on bf16x3: the
+    effective skip weights +-4, +-8 have one bf16 plane, and so has everything the two-plane weight-gradient unit reads."""
+    for name in NEW_SDF:
+        for core in mx.CORES:
+            cert = mx.certificate(mx.ALL_CASES[name], core)
+            assert cert.ok, (name, core, cert.failures[:3])
+    assert not set(NEW_SDF) & X3_NOT_CERTIFIED
+
+
+def test_skip_magnitudes_are_found_not_written_down():
+    case = mx.SDF_SKIP_CASES['w64_h3_s2_p213']
+    shapes = [tuple(case.state['lin%d.weight' % l].shape) for l in range(4)]
+    assert shapes == [(64, 3), (61, 64), (64, 64), (17, 64)]
+    s32 = mx.skip_scale(shapes, (2,), 16)
+    # the rule's scale is a C float: it reads back as the Python float of float32(1 / sqrt(2))
+    assert isinstance(s32, float) and s32 == torch.tensor(0.5).sqrt().item()
+    v4, v8 = mx.skip_magnitudes(s32)
+    s = torch.tensor(s32, dtype=torch.float32)
+    for v, k in ((v4, 4.0), (v8, 8.0)):
+        t = torch.tensor(v, dtype=torch.float32)
+        assert t.item() == v and (s * t).item() == k and (s * -t).item() == -k
+        assert abs(v - k * 2 ** 0.5) <= 4 * 2.0 ** -21            # within 4 ulp (ulp of [4, 16): 2^-21, 2^-20)
+    assert v8 == 2 * v4
+    # no such weight exists for 3 or 12: the skip layer uses +-4 and +-8 only
+    for k in (3.0, 12.0):
+        t = torch.tensor(k * 2 ** 0.5, dtype=torch.float32)
+        lo = hi = t
+        for _ in range(64):
+            assert (s * lo).item() != k and (s * hi).item() != k
+            lo, hi = torch.nextafter(lo, torch.tensor(0.0)), torch.nextafter(hi, torch.tensor(100.0))
+
+
+@pytest.mark.parametrize('name', [n for n in NEW_SDF if mx.ALL_CASES[n].args['skip_in']])
+def test_skip_cases_keep_softplus_at_relu_and_are_the_reference_module(name):
+    case = mx.ALL_CASES[name]
+    a = case.args
+    hid, (l,) = a['hidden'], a['skip_in']
+    assert case.state['lin%d.weight' % (l - 1)].shape[0] == a['width'] - 3
+    assert case.state['lin%d.weight' % l].shape == (a['width'], a['width'])
+    We = mx.effective_weight(case, l)
+    assert set(We.abs().unique().tolist()) == {0.0, 4.0, 8.0}
+    assert ((We[:, :-3] != 0).sum(1) == 2).all() and ((We[:, -3:] != 0).sum(1) == 1).all()
+    for i in range(hid):
+        W, b = mx.effective_weight(case, i), case.state['lin%d.bias' % i]
+        assert torch.equal(W % 4, torch.zeros_like(W)) and torch.equal(b % 4, torch.full_like(b, 2))
+    pre = mx.products(case)[2]
+    assert len(pre) == hid and not mx.check_preactivations(pre)
+    for p in pre:
+        assert (p >= 2).any() and (p <= -2).any()
+    # the module the reference defines -- cat([h, x]) / sqrt(2) @ W^T in float64 with the STORED weights -- against the
+    # effective-weight network.  Only the skip layer differs, each weight by a factor 1 + d with |d| <= 2^-23 (two fp32
+    # roundings: of 1 / sqrt(2) and of the product), so every output differs by at most 2^-23 of the sum of its terms'
+    # magnitudes M (the same network on |W|, |b|, |x|; ReLU is monotone and 1-Lipschitz, no switch flips at |a| >= 2):
+    # 1.2e-7 M, inside 1e-6 relative.  (Relative to an output itself, where terms cancel, up to 1.1e-6 was measured.)
+    x = case.inputs['x'].double()
+    h, m = x, x.abs()
+    for i in range(hid + 1):
+        W, b = case.state['lin%d.weight' % i].double(), case.state['lin%d.bias' % i].double()
+        if i == l:
+            h, m = torch.cat([h, x], 1) / 2 ** 0.5, torch.cat([m, x.abs()], 1) / 2 ** 0.5
+        h, m = h @ W.t() + b, m @ W.abs().t() + b.abs()
+        if i < hid:
+            assert (h.abs() > 1.9).all()
+            h = torch.relu(h)
+    ref = mx.reference(case)
+    exact = torch.cat([ref.get('sdf_raw', ref['sdf']), ref['feat']], 1)
+    assert ((h - exact).abs() <= 2.0 ** -23 * m).all() and ((h - exact).abs() <= 1e-6 * m).all()
+    assert (h - exact).abs().max() > 0
+
+
+def test_skip_gradient_is_scaled_once_and_stays_fp32():
+    """The expected gradient of the stored skip weights is float32(s32) * float32(G), G the exact integer gradient of the
+    effective weights with |G| < 2^24 (certified: the 'scaled_gradient' sum): one rounding, an fp32 value; the bias
+    gradient is unscaled (an integer)."""
+    for name in NEW_SDF:
+        case = mx.ALL_CASES[name]
+        for l in case.args['skip_in']:
+            ref = mx.reference(case)
+            sums = dict((n, mag) for n, mag, _ in mx.other_sums(case))
+            G = sums['l%d.scaled_gradient' % l]
+            assert torch.equal(G, G.round()) and G.max() < 2.0 ** 24 and G.max() > 0
+            got = ref['lin%d.weight' % l]
+            assert torch.equal(got.abs(), mx.scaled_gradient(case, G)) and torch.equal(got.float().double(), got)
+            assert not torch.equal(got, got.round())
+            bg = ref['lin%d.bias' % l]
+            assert torch.equal(bg, bg.round()) and bg.any()
+
+
+def test_skip_cases_cover_the_widths_and_sizes():
+    args = [c.args for c in mx.SDF_SKIP_CASES.values()]
+    assert {(a['width'], a['hidden'], a['skip_in']) for a in args} == \
+        {(64, 3, (2,)), (48, 2, (1,)), (100, 3, (2,)), (176, 4, (2,)), (227, 3, (2,))}
+    assert {a['P'] for a in args} == {1, 17, 63, 65, 213}
+    kts = {mx.build_plan(c).plan.layer[c.args['skip_in'][0]].kt for c in mx.SDF_SKIP_CASES.values()}
+    assert kts == {7, 6, 10, 14, mx.MT}
+    for c in mx.SDF_SKIP_CASES.values():
+        st = mx.structure(c, 'fp32')
+        l, = c.args['skip_in']
+        w = st['l%d.wgrad' % l]
+        assert w['two_part'] and w['parts'][1] == (16 * w['skip_tile'], 48) and w['kt'] == w['skip_tile'] + 3
+        assert st['l%d.fwd' % l]['k'] in (w['kt'], 16) and st['l%d.sweep' % l]['out_tiles'] == w['kt']
+        assert st['l%d.down' % l]['out_tiles'] == w['kt'] and st['l%d.up' % l]['k'] == st['l%d.fwd' % l]['k']
+    clamp = [c.args for c in mx.SDF_CLAMP_CASES.values()]
+    assert {a['width'] for a in clamp} == {64, 100} and {a['P'] for a in clamp} == {65, 213}
+    assert any(a['skip_in'] for a in clamp) and {(a['radius'], a['sphere_scale']) for a in clamp} == {(2.5, 1.0), (3.0, 0.5)}
+
+
+def test_a_skip_layer_at_width_256_does_not_fit():
+    """253 outputs are 16 tiles; with the input block behind them the skip layer has 19 > MT in-tiles: the plan refuses."""
+    from monosdf_amd import plan as planlib
+    with pytest.raises(RuntimeError, match='tile'):
+        planlib.build_sdf_plan([(256, 3), (253, 256), (256, 256), (17, 256)], (2,), 0, 0, False, 16)
+    planlib.build_sdf_plan([(227, 3), (224, 227), (227, 227), (17, 227)], (2,), 0, 0, False, 16)
+
+
+@pytest.mark.parametrize('name', [n for n in NEW_SDF if mx.ALL_CASES[n].args['radius'] > 0])
+def test_clamp_cases_hold_every_kind_of_point(name):
+    case = mx.ALL_CASES[name]
+    a = case.args
+    assert not mx.clamp_conditions(case)
+    n_clamp, n_feat, split = mx.groups(case)
+    c = mx.clamp_restatement(case)
+    x = case.inputs['x']
+    assert torch.equal(x, x.round()) and torch.equal(x[:len(mx.SPECIAL_POINTS)], torch.tensor(mx.SPECIAL_POINTS).float())
+    assert not x[0].any() and not x[-1].any()
+    # integer and power-of-two norms come out exactly, whatever the sqrt
+    assert c.nx[:12].tolist() == [0, 1, 2, 4, 3, 3, 3, 7, 7, 5, 5, 5]
+    ref = mx.reference(case)
+    raw = ref['sdf_raw'][:, 0]
+    assert ((raw - c.sph).abs() >= mx.CLAMP_MARGIN).all()
+    clamped = (torch.arange(a['P']) < n_clamp) & (c.sph < raw)
+    assert torch.equal(ref['sdf'][:, 0], torch.where(clamped, c.sph, raw))
+    assert torch.equal(ref['grad'][clamped], c.normals[clamped]) and torch.equal(ref['grad'][~clamped], ref['grad_raw'][~clamped])
+    if n_clamp > 0:
+        # the origin: clamped, sdf = scale * r, normals 0 (torch's minimum gives the point a zero gradient)
+        assert clamped[0] and ref['sdf'][0, 0] == a['sphere_scale'] * a['radius'] and (ref['grad'][0] == 0).all()
+    # float64 autograd agrees with the fp32 restatement to fp32 rounding on the clamped rows
+    x64 = x.double().requires_grad_()
+    sph64 = a['sphere_scale'] * (a['radius'] - x64.norm(dim=1))
+    n64, = torch.autograd.grad(sph64.sum(), x64)
+    assert (c.sph - sph64.detach()).abs().max() <= 2.0 ** -22 and (c.normals - n64).abs().max() <= 2.0 ** -22
+
+
+def test_group_cases_cover_every_value():
+    args = [c.args for c in mx.SDF_GROUP_CASES.values()]
+    assert all((a['width'], a['hidden'], a['P']) == (64, 2, 150) and a['radius'] > 0 for a in args)
+    assert {a['n_feat'] for a in args} == {0, 1, 16, 63, 64, 65, 150}
+    assert {a['n_clamp'] for a in args} == {0, 17, 64, 150}
+    assert {a['split'] for a in args} == {0, 15, 64, 129, 150}
+    assert any(len({a['n_clamp'], a['n_feat'], a['split']}) == 3 and
+               all(v % 16 for v in (a['n_clamp'], a['n_feat'], a['split'])) for a in args)
+    for c in mx.SDF_GROUP_CASES.values():
+        s, P = c.args['split'], c.args['P']
+        assert c.up['a'][0].shape == (s, 1) and c.up['a'][1] is None
+        assert c.up['C'][0].shape == (s, 3) and c.up['C'][1].shape == (P - s, 3) and c.up['B'].shape == (P, 16)
+        ref = mx.reference(c)
+        assert ref['feat'].shape == (c.args['n_feat'], 16) and ref['sdf'].shape == (P, 1)
+
+
+SKIP = {'skip.' + n: c for n, c in mx.SDF_SKIP_CASES.items()}
+CLAMP = {'clamp.' + n: c for n, c in mx.SDF_CLAMP_CASES.items()}
+GROUP = {'group.' + n: c for n, c in mx.SDF_GROUP_CASES.items()}
+
+
+def _noticed(mutation, cases):
+    """{case: the outputs that differ} over the cases, certified on all three cores, on which the mistake shows."""
+    hit = {}
+    for name, case in cases.items():
+        assert all(mx.certificate(case, core).ok for core in mx.CORES)
+        ref, got = mx.reference(case), mx.mutated_outputs(case, mutation)
+        assert set(got) == set(ref)
+        diff = sorted(k for k in ref if got[k].shape != ref[k].shape or not torch.equal(got[k], ref[k]))
+        if diff:
+            hit[name] = diff
+    return hit
+
+
+def test_every_mutation_is_listed():
+    assert set(mx.MUTATIONS) == {m for m, _, _ in MUTATION_TEETH}
+    for case in list(SKIP.values())[:1] + list(GROUP.values())[:1]:
+        ref, same = mx.reference(case), mx._sdf_products(case)[1]
+        assert all(torch.equal(same[k], ref[k]) for k in ref)
+
+
+# mutation, the cases it must show on, outputs that must be among the differing ones
+MUTATION_TEETH = [
+    ('one_input_arrival', SKIP, {'grad'}),
+    ('no_input_columns', SKIP, set()),
+    ('scale_twice', SKIP, set()),
+    ('no_scale', SKIP, set()),
+    ('clamp_all', GROUP, {'sdf', 'grad'}),
+    ('clamped_live', dict(CLAMP, **GROUP), {'lin0.weight', 'lin0.bias'}),
+    ('no_feat_grad_when_clamped', dict(CLAMP, **GROUP), {'lin0.weight'}),
+    ('feat_row_n_feat', GROUP, {'lin2.weight', 'lin2.bias'}),
+    ('second_tensor_at_pt', GROUP, {'lin0.weight'}),
+]
+
+
+@pytest.mark.parametrize('mutation,cases,keys', MUTATION_TEETH, ids=[m for m, _, _ in MUTATION_TEETH])
+def test_each_mistake_changes_a_certified_expected_value(mutation, cases, keys):
+    """The pass restated with one mistake in it (mlp_exact_cases.MUTATIONS): an expected value of a case certified on
+    all three cores changes, so the bit-exact comparison on the GPU sees that mistake."""
+    hit = _noticed(mutation, cases)
+    assert hit, mutation
+    assert any(keys <= set(d) for d in hit.values()), (mutation, hit)
+    if cases is SKIP:
+        # every skip case notices, in the skip layer's own weight gradient (or in d sdf / d x)
+        assert set(hit) == set(SKIP), (mutation, sorted(set(SKIP) - set(hit)))
+        if mutation != 'one_input_arrival':
+            for name, d in hit.items():
+                assert d == ['lin%d.weight' % SKIP[name].args['skip_in'][0]], (name, d)
+    if mutation == 'clamp_all':
+        # shows exactly where n_clamp < P
+        assert set(hit) == {n for n, c in GROUP.items() if c.args['n_clamp'] < c.args['P']}
+    if mutation == 'feat_row_n_feat':
+        assert set(hit) == {n for n, c in GROUP.items() if c.args['n_feat'] < c.args['P']}
+    if mutation == 'second_tensor_at_pt':
+        # every row from `split` on reads another row of the second tensor, or past its end
+        assert set(hit) == {n for n, c in GROUP.items() if 0 < c.args['split'] < c.args['P']}
+    if mutation == 'clamped_live':
+        assert set(hit) >= set(CLAMP)
+
+
+def test_point_groups_do_not_change_what_a_point_gets():
+    """Both forms of the output layer and both gradient tensors carry the same exact integers: a row's sdf, features and
+    gradient depend on the groups only through the clamp (cases of one seed share network and points)."""
+    by_seed = {}
+    for n, c in mx.SDF_GROUP_CASES.items():
+        by_seed.setdefault(tuple(c.inputs['x'].flatten().tolist()), []).append(c)
+    assert max(len(v) for v in by_seed.values()) >= 2
+    for cs in by_seed.values():
+        for c in cs[1:]:
+            r0, r1 = mx.reference(cs[0]), mx.reference(c)
+            assert torch.equal(r0['sdf_raw'], r1['sdf_raw']) and torch.equal(r0['grad_raw'], r1['grad_raw'])
+            k = min(cs[0].args['n_feat'], c.args['n_feat'])
+            assert torch.equal(r0['feat'][:k], r1['feat'][:k])
