@@ -11,10 +11,11 @@ dtu_eval/eval.py (csrc/dtueval.hip, ABI msdf_dtu_*; the closing distance queries
 * ``evaluate_dtu``: the rest of eval.py: bounding box, observation mask, the two one-sided Chamfer means.
 * ``read_dtu_scene``, ``read_masks``: the official ObsMask / Plane / stl files; a scene's mask images or an ``.npy`` stack.
 
-Everything runs on CUDA tensors; there is no CPU path.  Every rule is integer, boolean, separately rounded fp32 or
-fp64, with no floating-point atomics: the same inputs give bitwise the same outputs every call, and the numpy
-restatements of tests/dtu_numpy.py are matched exactly.  Not built: the two coloured error clouds
-``vis_*_d2s.ply`` / ``vis_*_s2d.ply`` that eval.py also writes.
+Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function
+that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_lattice``.  Every rule is
+integer, boolean, separately rounded fp32 or fp64, with no floating-point atomics: the same inputs give bitwise the
+same outputs every call, and the numpy restatements of tests/dtu_numpy.py are matched exactly.  Not built: the two
+coloured error clouds ``vis_*_d2s.ply`` / ``vis_*_s2d.ply`` that eval.py also writes.
 """
 import glob
 import os
@@ -22,9 +23,9 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
-from .mesh import Mesh
-from .mesh_eval import _check_cloud, _check_mesh, _mesh_tensors, nearest_neighbors, read_ply
+from . import mesh_args as ma
+from .mesh import Mesh, read_ply
+from .mesh_eval import nearest_neighbors
 
 MAX_RADIUS = 32                      # pixels: the dilation kernel reads a word and its two neighbours
 _CELL_AXIS_MAX = 2 ** 21             # cells per axis the 63-bit cell key holds
@@ -32,15 +33,11 @@ _CELL_SLACK = 1.0 + 2.0 ** -10       # cell side over radius: rounding of the ce
 
 
 def _check_images(name, arg, t):
-    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
-        raise TypeError('%s: %s must be a CUDA tensor (there is no CPU path), got %s' %
-                        (name, arg, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-    if t.dtype not in (torch.uint8, torch.bool):
-        raise TypeError('%s: %s must be uint8 or bool, got %s' % (name, arg, t.dtype))
-    if t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 1:
-        raise ValueError('%s: %s must be [n, H, W], got %s' % (name, arg, tuple(t.shape)))
-    if t.shape[0] * t.shape[1] * t.shape[2] > 2 ** 37 or max(t.shape) >= 2 ** 31:
-        raise ValueError('%s: %s of shape %s is too large' % (name, arg, tuple(t.shape)))
+    """[n, H, W] uint8 / bool masks -> contiguous uint8 (a bool tensor viewed, not copied)."""
+    ma.check_tensor(name, arg, t, (torch.uint8, torch.bool), '[n, H, W]')
+    if t.shape[1] < 1 or t.shape[2] < 1 or t.numel() > 2 ** 37:
+        raise ValueError('%s: %s must be [n, H, W] with H, W >= 1 and at most 2^37 pixels, got %s' %
+                         (name, arg, tuple(t.shape)))
     return (t.view(torch.uint8) if t.dtype == torch.bool else t).contiguous()
 
 
@@ -56,10 +53,9 @@ def dilate_masks(masks, radius=12):
     n, h, w = m.shape
     out = torch.empty(n, h, w, dtype=torch.uint8, device=m.device)
     if n > 0:
-        lib = _lib.load()
         with torch.cuda.device(m.device):
-            ws = torch.empty(int(lib.msdf_dtu_dilate_workspace_bytes(n, h, w)), dtype=torch.uint8, device=m.device)
-            _lib.call('msdf_dtu_dilate', _lib.ptr(m), n, h, w, r, _lib.ptr(ws), _lib.ptr(out), _lib.stream_ptr())
+            ws = ma.workspace('dilate_masks', 'msdf_dtu_dilate_workspace_bytes', n, h, w, device=m.device)
+            ma.call('msdf_dtu_dilate', m, n, h, w, r, ws, out)
     return out
 
 
@@ -108,20 +104,18 @@ def mask_vertices(vertices, projections, dilated):
     align_corners=True)``, which scales them back: a vertex within fp32 rounding of a pixel boundary or of the image
     edge may fall on the other side there."""
     name = 'mask_vertices'
-    _check_cloud(name, 'vertices', vertices)
+    ma.check_tensor(name, 'vertices', vertices, shape='[V, 3]')
     proj = _projection_rows(name, projections)
     d = _check_images(name, 'dilated', dilated)
-    if d.device != vertices.device:
-        raise ValueError('%s: vertices on %s, dilated on %s' % (name, vertices.device, d.device))
+    ma.same_device(name, vertices=vertices, dilated=d)
     if d.shape[0] != proj.shape[0]:
         raise ValueError('%s: %d projections for %d masks' % (name, proj.shape[0], d.shape[0]))
     v = vertices.contiguous()
     keep = torch.ones(v.shape[0], dtype=torch.uint8, device=v.device)
     if v.shape[0] > 0 and d.shape[0] > 0:
-        proj = torch.from_numpy(proj).to(v.device)
         with torch.cuda.device(v.device):
-            _lib.call('msdf_dtu_mask_vertices', _lib.ptr(v), v.shape[0], _lib.ptr(proj), d.shape[0], _lib.ptr(d),
-                      d.shape[1], d.shape[2], _lib.ptr(keep), _lib.stream_ptr())
+            ma.call('msdf_dtu_mask_vertices', v, v.shape[0], ma.upload(proj, v.device), d.shape[0], d, d.shape[1],
+                    d.shape[2], keep)
     return keep.bool()
 
 
@@ -134,21 +128,15 @@ def cull_to_masks(mesh, projections, masks, radius=12):
     and keeps all vertices.  ``mesh``: a Mesh or a (vertices, faces) pair.  -> Mesh (with the kept vertices' normals
     when a Mesh came in).  The caller takes the result to the world frame with ``Mesh.apply_transform(scale_mat)``."""
     name = 'cull_to_masks'
-    nrm = mesh.vertex_normals if isinstance(mesh, Mesh) else None
-    v, f = _mesh_tensors(mesh, name)
+    v, f, nrm = ma.mesh_tensors(name, mesh, ma.device_of(masks))
     if isinstance(masks, np.ndarray):
-        masks = torch.from_numpy(np.ascontiguousarray(masks != 0).view(np.uint8)).to(v.device)
-    if f.shape[0] > 0 and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
-        raise ValueError('%s: face index outside [0, %d)' % (name, v.shape[0]))
+        masks = ma.upload((masks != 0).view(np.uint8), v.device)
     keep = mask_vertices(v, projections, dilate_masks(masks, radius))
-    f = f.long()
-    new_index = torch.cumsum(keep.long(), 0) - 1
-    face_keep = keep[f].all(dim=1) if f.shape[0] > 0 else torch.zeros(0, dtype=torch.bool, device=v.device)
-    faces = new_index[f[face_keep]].cpu().numpy().reshape(-1, 3)
+    faces = ma.compact_faces(keep, f).cpu().numpy()
+    if nrm is None:                                    # a (vertices, faces) pair
+        return Mesh(v[keep].double().cpu().numpy(), faces)
     keep_h = keep.cpu().numpy()
-    if isinstance(mesh, Mesh):
-        return Mesh(mesh.vertices[keep_h], faces, nrm[keep_h])
-    return Mesh(v[keep].double().cpu().numpy(), faces)
+    return Mesh(mesh.vertices[keep_h], faces, nrm[keep_h])
 
 
 def sample_lattice(vertices, faces, density=0.2):
@@ -159,38 +147,34 @@ def sample_lattice(vertices, faces, density=0.2):
     a = (i + 0.5) / max(n1, 1e-7) for i = 0..n1 and b = (j + 0.5) / max(n2, 1e-7) for j = 0..n2, kept iff a + b < 1;
     point = (v1 a + v2 b) + p0, rounded once to fp32.  Output order: face ascending, then i, then j.  The vertices
     themselves are not included: the caller concatenates them, as the reference does.  ValueError at 2^31 points."""
-    name = 'sample_lattice'
+    dens = _density('sample_lattice', density)
+    return _lattice(*ma.mesh_tensors('sample_lattice', (vertices, faces))[:2], dens)
+
+
+def _density(name, density):
     dens = float(density)
     if not (dens > 0.0 and np.isfinite(dens)):
         raise ValueError('%s: density must be positive and finite, got %r' % (name, density))
-    _check_mesh(name, vertices, faces)
-    dev = vertices.device
-    v = vertices.contiguous()
-    nv, nf = v.shape[0], faces.shape[0]
+    return dens
+
+
+def _lattice(v, f, dens):
+    dev = v.device
+    nv, nf = v.shape[0], f.shape[0]
     if nf == 0:
         return v.new_empty(0, 3)
-    if nf >= 2 ** 31:
-        raise ValueError('%s: %d faces: int32 indices hold fewer than 2^31' % (name, nf))
-    ok = torch.stack([torch.isfinite(v).all(), faces.min() >= 0, faces.max() < nv]).cpu().tolist()
-    if not ok[0]:
-        raise ValueError('%s: non-finite vertex coordinates' % name)
-    if not (ok[1] and ok[2]):
-        raise ValueError('%s: face index outside [0, %d)' % (name, nv))
-    f = faces.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
         offsets = torch.zeros(nf + 1, dtype=torch.int64, device=dev)
         counts = offsets[1:]
-        _lib.call('msdf_dtu_lattice_count', _lib.ptr(v), nv, _lib.ptr(f), nf, dens, _lib.ptr(counts),
-                  _lib.stream_ptr())
+        ma.call('msdf_dtu_lattice_count', v, nv, f, nf, dens, counts)
         largest = int(counts.max())
         counts.cumsum_(0)                                    # offsets: the exclusive scan, the total last
         total = int(offsets[-1])
         if largest >= 2 ** 31 or total >= 2 ** 31:
-            raise ValueError('%s: 2^31 points or more (density %g): sample the mesh in parts' % (name, dens))
+            raise ValueError('sample_lattice: 2^31 points or more (density %g): sample the mesh in parts' % dens)
         out = torch.empty(total, 3, dtype=torch.float32, device=dev)
         if total > 0:
-            _lib.call('msdf_dtu_lattice_emit', _lib.ptr(v), nv, _lib.ptr(f), nf, dens, _lib.ptr(offsets), total,
-                      _lib.ptr(out), _lib.stream_ptr())
+            ma.call('msdf_dtu_lattice_emit', v, nv, f, nf, dens, offsets, total, out)
     return out
 
 
@@ -220,14 +204,13 @@ def radius_thin(points, radius, order=None, return_rounds=False):
             raise ValueError('%s: order must be a 1-D int64 tensor' % name)
         if isinstance(points, torch.Tensor) and points.dim() == 2 and order.shape[0] != points.shape[0]:
             raise ValueError('%s: order has %d entries for %d points' % (name, order.shape[0], points.shape[0]))
-    _check_cloud(name, 'points', points)
+    ma.check_tensor(name, 'points', points)
     dev = points.device
     n = points.shape[0]
     pts = points.contiguous()
     rank = None
     if order is not None:
-        if order.device != dev:
-            raise ValueError('%s: points on %s, order on %s' % (name, dev, order.device))
+        ma.same_device(name, points=points, order=order)
         if n > 0:
             inside = (order >= 0) & (order < n)
             hit = torch.zeros(n, dtype=torch.bool, device=dev)
@@ -239,28 +222,22 @@ def radius_thin(points, radius, order=None, return_rounds=False):
     keep = torch.zeros(n, dtype=torch.uint8, device=dev)
     rounds = 0
     if n > 0:
-        lo, hi = torch.aminmax(pts, dim=0)
-        lo_h, hi_h = lo.double().cpu(), hi.double().cpu()
-        if not bool(torch.isfinite(lo_h).all() and torch.isfinite(hi_h).all()):
-            raise ValueError('%s: non-finite coordinates' % name)
+        _, lo_h, hi_h = ma.finite_bounds(name, pts)
         # two points within r differ by less than one cell per axis, rounding included; at most 2^21 - 4 cells an axis
         cell = max(r * _CELL_SLACK, float((hi_h - lo_h).max()) / (_CELL_AXIS_MAX - 4))
-        lib = _lib.load()
         with torch.cuda.device(dev):
             keys = torch.empty(n, dtype=torch.int64, device=dev)
-            _lib.call('msdf_dtu_thin_keys', _lib.ptr(pts), n, float(lo_h[0]), float(lo_h[1]), float(lo_h[2]), cell,
-                      _lib.ptr(keys), _lib.stream_ptr())
+            ma.call('msdf_dtu_thin_keys', pts, n, *lo_h.tolist(), cell, keys)
             sorted_keys, perm = torch.sort(keys, stable=True)
-            ws = torch.empty(int(lib.msdf_dtu_thin_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-            _lib.call('msdf_dtu_thin_prepare', _lib.ptr(pts), _lib.ptr(perm), _lib.ptr(rank), _lib.ptr(sorted_keys),
-                      n, _lib.ptr(ws), _lib.stream_ptr())
+            ws = ma.workspace(name, 'msdf_dtu_thin_workspace_bytes', n, device=dev)
+            ma.call('msdf_dtu_thin_prepare', pts, perm, rank, sorted_keys, n, ws)
             undecided = torch.empty(1, dtype=torch.int32, device=dev)
             while True:
-                _lib.call('msdf_dtu_thin_round', _lib.ptr(ws), n, r, _lib.ptr(undecided), _lib.stream_ptr())
+                ma.call('msdf_dtu_thin_round', ws, n, r, undecided)
                 rounds += 1
                 if int(undecided.item()) == 0:
                     break
-            _lib.call('msdf_dtu_thin_finish', _lib.ptr(ws), _lib.ptr(perm), n, _lib.ptr(keep), _lib.stream_ptr())
+            ma.call('msdf_dtu_thin_finish', ws, perm, n, keep)
     return (keep.bool(), rounds) if return_rounds else keep.bool()
 
 
@@ -289,19 +266,14 @@ def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0
     their mean.  -> a dict of Python floats (nan where no distance is below max_dist).  ``return_clouds``: also a dict
     with 'data_pcd', 'order', 'keep', 'data_in', 'data_in_obs', 'stl_above', 'dist_d2s', 'dist_s2d' (tensors)."""
     name = 'evaluate_dtu'
-    if isinstance(mesh_or_points, (Mesh, tuple, list)):
-        v, f = _mesh_tensors(mesh_or_points, name)
-        cloud = torch.cat([v.contiguous(), sample_lattice(v, f, density)])
+    dev = ma.device_of(stl_points, obs_mask)
+    if isinstance(mesh_or_points, (tuple, list)) or hasattr(mesh_or_points, 'faces'):
+        v, f, _ = ma.mesh_tensors(name, mesh_or_points, dev)
+        cloud = torch.cat([v, _lattice(v, f, _density(name, density))])
     else:
-        cloud = mesh_or_points
-        if isinstance(cloud, np.ndarray):
-            cloud = torch.from_numpy(np.ascontiguousarray(cloud, np.float32)).cuda()
-        _check_cloud(name, 'points', cloud)
+        cloud = ma.cloud_tensor(name, 'points', mesh_or_points, dev)
     dev = cloud.device
-    stl = stl_points
-    if isinstance(stl, np.ndarray):
-        stl = torch.from_numpy(np.ascontiguousarray(stl[:, :3], np.float32)).to(dev)
-    _check_cloud(name, 'stl_points', stl)
+    stl = ma.cloud_tensor(name, 'stl_points', stl_points, dev)
     obs = obs_mask if isinstance(obs_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(obs_mask))
     if obs.dim() != 3:
         raise ValueError('%s: obs_mask must be [X, Y, Z], got %s' % (name, tuple(obs.shape)))
@@ -322,12 +294,12 @@ def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0
         order = torch.randperm(n, generator=gen, device=dev)
     keep = radius_thin(cloud, density, order)
     data_down = cloud[keep]
-    lower = torch.from_numpy((bb32[0] - np.float32(patch)).astype(np.float64)).to(dev)
-    upper = torch.from_numpy((bb32[1] + np.float32(patch * 2)).astype(np.float64)).to(dev)
+    lower = ma.upload((bb32[0] - np.float32(patch)).astype(np.float64), dev)
+    upper = ma.upload((bb32[1] + np.float32(patch * 2)).astype(np.float64), dev)
     down64 = data_down.double()
     inbound = ((down64 >= lower) & (down64 < upper)).all(dim=1)
     data_in = data_down[inbound]
-    grid = torch.round((data_in.double() - torch.from_numpy(bb32[0].astype(np.float64)).to(dev)) / res).long()
+    grid = torch.round((data_in.double() - ma.upload(bb32[0].astype(np.float64), dev)) / res).long()
     shape = torch.tensor(list(obs.shape), dtype=torch.int64, device=dev)
     grid_in = ((grid >= 0) & (grid < shape)).all(dim=1)
     g = grid[grid_in]

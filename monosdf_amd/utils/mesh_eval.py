@@ -7,31 +7,21 @@
 * ``sample_surface``, ``face_normals``: trimesh.sample.sample_surface and Trimesh.face_normals (eval_recon.py:138-158).
 * ``evaluate_scannet``: ``evaluate`` (evaluate.py:29-56).  ``evaluate_replica``: the metrics of ``calc_3d_metric``
   (eval_recon.py:138-177).
-* ``read_ply``: ASCII / binary little-endian PLY meshes written by other programs.
+* ``read_ply``: utils/mesh.py's PLY reader, importable from here as before.
 
-Everything runs on CUDA tensors; there is no CPU path.  Out of scope: ICP alignment (``get_align_transformation``),
-the oriented-bounding-box crop of ``calc_3d_metric`` (eval_recon.py:121-136), and any grid- or tree-accelerated search:
-brute force is the exact baseline a later one is checked against.  View culling and TSDF re-fusion (``refuse``), which
-the reference applies to the predicted mesh before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol
-and its mask culling are in utils/mesh_dtu.py.
+Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function
+that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_face_cross``.
+Out of scope: ICP alignment (``get_align_transformation``), the oriented-bounding-box crop of ``calc_3d_metric``
+(eval_recon.py:121-136), and any grid- or tree-accelerated search: brute force is the exact baseline a later one is
+checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to the predicted mesh
+before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol and its mask culling are in
+utils/mesh_dtu.py.
 """
 import numpy as np
 import torch
 
-from .. import _lib
-from .mesh import Mesh
-
-
-def _check_cloud(name, arg, t):
-    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
-        raise TypeError('%s: %s must be a CUDA tensor (there is no CPU path), got %s' %
-                        (name, arg, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-    if t.dtype != torch.float32:
-        raise TypeError('%s: %s must be float32, got %s' % (name, arg, t.dtype))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError('%s: %s must be [N, 3], got %s' % (name, arg, tuple(t.shape)))
-    if t.shape[0] >= 2 ** 31:
-        raise ValueError('%s: %s has %d points: int32 indices hold fewer than 2^31' % (name, arg, t.shape[0]))
+from . import mesh_args as ma
+from .mesh import read_ply                                   # noqa: F401 (public here too)
 
 
 def nearest_neighbors(reference, query, n_splits=0):
@@ -43,25 +33,22 @@ def nearest_neighbors(reference, query, n_splits=0):
     The same inputs give bitwise the same outputs every call and for every ``n_splits`` (over how many slices of the
     reference cloud the work is spread; 0 = chosen from the sizes).  ValueError for an empty reference cloud and for
     non-finite coordinates (one device reduction and one host read)."""
-    _check_cloud('nearest_neighbors', 'reference', reference)
-    _check_cloud('nearest_neighbors', 'query', query)
-    if reference.device != query.device:
-        raise ValueError('nearest_neighbors: reference on %s, query on %s' % (reference.device, query.device))
+    name = 'nearest_neighbors'
+    ma.check_tensor(name, 'reference', reference)
+    ma.check_tensor(name, 'query', query)
+    dev = ma.same_device(name, reference=reference, query=query)
     R, Q = reference.shape[0], query.shape[0]
     if R == 0:
-        raise ValueError('nearest_neighbors: the reference cloud is empty')
-    dev = query.device
+        raise ValueError('%s: the reference cloud is empty' % name)
     ref, qry = reference.contiguous(), query.contiguous()
     if not bool((torch.isfinite(ref).all() & torch.isfinite(qry).all()).item()):
-        raise ValueError('nearest_neighbors: non-finite coordinates')
+        raise ValueError('%s: non-finite coordinates' % name)
     dist = torch.empty(Q, dtype=torch.float32, device=dev)
     idx = torch.empty(Q, dtype=torch.int32, device=dev)
     if Q > 0:
-        lib = _lib.load()
         with torch.cuda.device(dev):
-            ws = torch.empty(int(lib.msdf_nn_workspace_bytes(R, Q, int(n_splits))), dtype=torch.uint8, device=dev)
-            _lib.call('msdf_nn_search', _lib.ptr(ref), R, _lib.ptr(qry), Q, int(n_splits), _lib.ptr(ws),
-                      _lib.ptr(dist), _lib.ptr(idx), _lib.stream_ptr())
+            ws = ma.workspace(name, 'msdf_nn_workspace_bytes', R, Q, int(n_splits), device=dev)
+            ma.call('msdf_nn_search', ref, R, qry, Q, int(n_splits), ws, dist, idx)
     return dist, idx.long()
 
 
@@ -78,55 +65,48 @@ def voxel_down_sample(points, voxel_size):
     Parity with open3d's own binning is UNVERIFIED: open3d is not available where this is built and the reference
     holds no recorded output of it, so the rule is pinned by the numpy restatement of the tests only (a point within
     rounding of a voxel face may fall on the other side there, and open3d's output order is its hash map's)."""
-    _check_cloud('voxel_down_sample', 'points', points)
+    name = 'voxel_down_sample'
+    ma.check_tensor(name, 'points', points)
     v = float(np.float32(voxel_size))
     if not v > 0.0:
-        raise ValueError('voxel_down_sample: voxel_size must be positive, got %r' % (voxel_size,))
+        raise ValueError('%s: voxel_size must be positive, got %r' % (name, voxel_size))
     n = points.shape[0]
     dev = points.device
     if n == 0:
         return points.new_empty(0, 3)
     pts = points.contiguous()
-    lo, hi = torch.aminmax(pts, dim=0)
-    lo_h, hi_h = lo.double().cpu(), hi.double().cpu()
-    if not bool(torch.isfinite(lo_h).all() and torch.isfinite(hi_h).all()):
-        raise ValueError('voxel_down_sample: non-finite coordinates')
+    lo, lo_h, hi_h = ma.finite_bounds(name, pts)
     if float(((hi_h - lo_h) / v).max()) + 2.0 >= _VOXEL_AXIS_MAX:
-        raise ValueError('voxel_down_sample: more than 2^21 voxels along an axis (extent %g, voxel %g)' %
-                         (float((hi_h - lo_h).max()), v))
+        raise ValueError('%s: more than 2^21 voxels along an axis (extent %g, voxel %g)' %
+                         (name, float((hi_h - lo_h).max()), v))
     with torch.cuda.device(dev):
         keys = torch.empty(n, dtype=torch.int64, device=dev)
-        _lib.call('msdf_voxel_keys', _lib.ptr(pts), n, _lib.ptr(lo.contiguous()), v, _lib.ptr(keys),
-                  _lib.stream_ptr())
+        ma.call('msdf_voxel_keys', pts, n, lo.contiguous(), v, keys)
         sorted_keys, order = torch.sort(keys, stable=True)
         head = torch.ones(n, dtype=torch.bool, device=dev)
         head[1:] = sorted_keys[1:] != sorted_keys[:-1]
         seg_start = head.nonzero().squeeze(1).contiguous()
         m = seg_start.shape[0]
         out = torch.empty(m, 3, dtype=torch.float32, device=dev)
-        _lib.call('msdf_voxel_mean', _lib.ptr(pts), _lib.ptr(order), _lib.ptr(seg_start), n, m, _lib.ptr(out),
-                  _lib.stream_ptr())
+        ma.call('msdf_voxel_mean', pts, order, seg_start, n, m, out)
     return out
 
 
-def _check_mesh(name, vertices, faces):
-    _check_cloud(name, 'vertices', vertices)
-    if not isinstance(faces, torch.Tensor) or faces.device != vertices.device:
-        raise TypeError('%s: faces must be a tensor on %s' % (name, vertices.device))
-    if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError('%s: faces must be an integer [F, 3] tensor' % name)
-
-
 def _face_cross(vertices, faces):
-    """origin, the two edge vectors and their cross product per face, in fp64."""
+    """origin, the two edge vectors and their cross product per face, in fp64.  Indexes with ``faces`` as they are:
+    only for a mesh that ``mesh_args.mesh_tensors`` has passed."""
     tri = vertices.double()[faces.long()]
     e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
     return tri[:, 0], e1, e2, torch.linalg.cross(e1, e2)
 
 
 def face_normals(vertices, faces):
-    """Unit normals by the right-hand rule, [F,3] float32; zero for degenerate (zero-area) faces."""
-    _check_mesh('face_normals', vertices, faces)
+    """Unit normals by the right-hand rule, [F,3] float32; zero for degenerate (zero-area) faces.  ValueError for a
+    face index outside [0, V) and for non-finite vertices (as in every function here that takes a mesh)."""
+    return _face_normals(*ma.mesh_tensors('face_normals', (vertices, faces))[:2])
+
+
+def _face_normals(vertices, faces):
     c = _face_cross(vertices, faces)[3]
     norm = c.norm(dim=1, keepdim=True)
     return torch.where(norm > 0, c / torch.where(norm > 0, norm, torch.ones_like(norm)),
@@ -138,7 +118,10 @@ def sample_surface(vertices, faces, count, generator=None):
     proportional to its area, a uniform point in it (the unit square folded onto the triangle).
     -> (points [count,3] float32, face_index [count] int64).  Degenerate (zero-area) faces are never drawn.
     ``generator``: a torch.Generator on the vertices' device; the same seed gives the same samples."""
-    _check_mesh('sample_surface', vertices, faces)
+    return _sample_surface(*ma.mesh_tensors('sample_surface', (vertices, faces))[:2], count, generator)
+
+
+def _sample_surface(vertices, faces, count, generator):
     dev = vertices.device
     origin, e1, e2, c = _face_cross(vertices, faces)
     cum = torch.cumsum(0.5 * c.norm(dim=1), 0)
@@ -155,16 +138,6 @@ def sample_surface(vertices, faces, count, generator=None):
     return pts.float(), face_index
 
 
-def _cloud(x, dev=None):
-    """A Mesh, a numpy array or a CUDA tensor -> float32 CUDA [N,3] (host data is uploaded; a CPU tensor is refused
-    by the functions that receive it)."""
-    if isinstance(x, Mesh):
-        x = x.vertices
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x[:, :3], np.float32)).to(dev or 'cuda')
-    return x
-
-
 def _fscore(p, r):
     return 2.0 * p * r / (p + r) if p + r > 0 else 0.0
 
@@ -177,12 +150,11 @@ def evaluate_scannet(pred_vertices, gt_vertices, threshold=0.05, down_sample=0.0
       'Comp'  mean distance from the target points to the predicted cloud      'Recal' share of them < threshold
       'F-score' 2 Prec Recal / (Prec + Recal), 0.0 when both are zero.
     The down-sample follows open3d's rule but its parity with open3d is unverified (see voxel_down_sample)."""
-    pred, gt = _cloud(pred_vertices), _cloud(gt_vertices)
+    dev = ma.device_of(pred_vertices, gt_vertices)
+    pred = ma.cloud_tensor('evaluate_scannet', 'pred_vertices', pred_vertices, dev)
+    gt = ma.cloud_tensor('evaluate_scannet', 'gt_vertices', gt_vertices, dev)
     if down_sample:
         pred, gt = voxel_down_sample(pred, down_sample), voxel_down_sample(gt, down_sample)
-    else:
-        _check_cloud('evaluate_scannet', 'pred_vertices', pred)
-        _check_cloud('evaluate_scannet', 'gt_vertices', gt)
     if pred.shape[0] == 0 or gt.shape[0] == 0:
         raise ValueError('evaluate_scannet: an empty cloud')
     dist1, _ = nearest_neighbors(pred, gt)              # target -> predicted
@@ -191,19 +163,6 @@ def evaluate_scannet(pred_vertices, gt_vertices, threshold=0.05, down_sample=0.0
                         (dist1 < threshold).double().mean()]).tolist()
     acc, comp, prec, recal = vals
     return {'Acc': acc, 'Comp': comp, 'Prec': prec, 'Recal': recal, 'F-score': _fscore(prec, recal)}
-
-
-def _mesh_tensors(m, name):
-    if isinstance(m, Mesh):
-        v, f = m.vertices, m.faces
-    else:
-        v, f = m
-    if isinstance(v, np.ndarray):
-        v = torch.from_numpy(np.ascontiguousarray(v, np.float32)).cuda()
-    if isinstance(f, np.ndarray):
-        f = torch.from_numpy(np.ascontiguousarray(f, np.int64)).to(v.device)
-    _check_mesh(name, v, f)
-    return v, f
 
 
 def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_samples=False):
@@ -220,13 +179,15 @@ def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_sam
     alignment and the oriented-bounding-box crop that ``calc_3d_metric`` applies first (pass meshes already aligned
     and cropped).  ``return_samples``: also a dict with 'rec_points', 'rec_faces', 'gt_points', 'gt_faces' (the samples
     and the face each came from), 'rec_normals', 'gt_normals' (per sample)."""
-    rv, rf = _mesh_tensors(rec, 'evaluate_replica')
-    gv, gf = _mesh_tensors(gt, 'evaluate_replica')
+    name = 'evaluate_replica'
+    rv, rf, _ = ma.mesh_tensors(name, rec, ma.device_of(*ma.mesh_parts(gt)))
+    gv, gf, _ = ma.mesh_tensors(name, gt, rv.device)
+    ma.same_device(name, rec=rv, gt=gv)
     gen = torch.Generator(device=rv.device)
     gen.manual_seed(int(seed))
-    rp, rfi = sample_surface(rv, rf, n_samples, gen)
-    gp, gfi = sample_surface(gv, gf, n_samples, gen)
-    rn, gn = face_normals(rv, rf)[rfi], face_normals(gv, gf)[gfi]
+    rp, rfi = _sample_surface(rv, rf, n_samples, gen)
+    gp, gfi = _sample_surface(gv, gf, n_samples, gen)
+    rn, gn = _face_normals(rv, rf)[rfi], _face_normals(gv, gf)[gfi]
     d_acc, i_gt = nearest_neighbors(gp, rp)             # rec -> gt
     d_comp, i_rec = nearest_neighbors(rp, gp)           # gt -> rec
     n_acc = (rn.double() * gn.double()[i_gt]).sum(1).abs().mean()
@@ -241,104 +202,3 @@ def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_sam
         return out, {'rec_points': rp, 'rec_faces': rfi, 'rec_normals': rn,
                      'gt_points': gp, 'gt_faces': gfi, 'gt_normals': gn}
     return out
-
-
-_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2',
-              'ushort': 'u2', 'uint16': 'u2', 'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4',
-              'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
-
-
-def _ply_header(data):
-    if data[:4] not in (b'ply\n', b'ply\r'):
-        raise ValueError('read_ply: not a PLY file')
-    end = data.find(b'end_header')
-    if end < 0:
-        raise ValueError('read_ply: no end_header')
-    body = data.index(b'\n', end) + 1
-    fmt, elements = None, []
-    for line in data[:end].decode('ascii').splitlines()[1:]:
-        w = line.split()
-        if not w or w[0] in ('comment', 'obj_info'):
-            continue
-        if w[0] == 'format':
-            fmt = w[1]
-        elif w[0] == 'element':
-            elements.append((w[1], int(w[2]), []))
-        elif w[0] == 'property':
-            if not elements:
-                raise ValueError('read_ply: property before element')
-            try:
-                if w[1] == 'list':
-                    elements[-1][2].append((w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
-                else:
-                    elements[-1][2].append((w[2], _PLY_TYPES[w[1]], None))
-            except KeyError as e:
-                raise ValueError('read_ply: unknown property type %s' % e)
-    if fmt not in ('ascii', 'binary_little_endian'):
-        raise ValueError('read_ply: format %r is not read (ascii and binary_little_endian are)' % fmt)
-    return fmt, elements, body
-
-
-def read_ply(path):
-    """A triangle mesh from an ASCII or binary little-endian PLY written by any program -> Mesh.  Vertex properties:
-    x, y, z found by name (float or double; nx, ny, nz too if present), every other scalar property skipped.  Faces:
-    the list property ``vertex_indices`` / ``vertex_index`` of any integer count and index type, triangles only; other
-    scalar face properties skipped.  A file without a face element gives a mesh without faces (a point cloud)."""
-    with open(path, 'rb') as fh:
-        data = fh.read()
-    fmt, elements, pos = _ply_header(data)
-    names = [e[0] for e in elements]
-    if 'vertex' not in names:
-        raise ValueError('read_ply: no vertex element')
-    wanted = names.index('face') if 'face' in names else names.index('vertex')
-    tokens = data[pos:].split() if fmt == 'ascii' else None
-    tpos = 0
-    verts = normals = None
-    faces = np.zeros((0, 3), np.int64)
-    for k, (name, count, props) in enumerate(elements[:wanted + 1]):
-        lists = [p for p in props if p[2] is not None]
-        if name == 'face':
-            if len(lists) != 1 or lists[0][0] not in ('vertex_indices', 'vertex_index'):
-                raise ValueError('read_ply: face element needs one list property vertex_indices')
-        elif lists:
-            raise ValueError('read_ply: list property in element %r' % name)
-        # the record of one row, lists taken as triangles (checked below)
-        fields = []
-        for pname, a, b in props:
-            if b is None:
-                fields.append((pname, '<' + a))
-            else:
-                fields += [(pname + '#n', '<' + a), (pname, '<' + b, (3,))]
-        dt = np.dtype(fields)
-        width = sum(3 if len(f) == 3 else 1 for f in fields)
-        if fmt == 'ascii':
-            flat = np.array(tokens[tpos:tpos + count * width], dtype=np.float64)
-            if flat.size != count * width:
-                raise ValueError('read_ply: file ends inside element %r (only triangle faces are read)' % name)
-            flat = flat.reshape(count, width)
-            tpos += count * width
-            rows, c = {}, 0
-            for f in fields:
-                w = 3 if len(f) == 3 else 1
-                rows[f[0]] = flat[:, c] if w == 1 else flat[:, c:c + 3]
-                c += w
-        else:
-            if pos + count * dt.itemsize > len(data):
-                raise ValueError('read_ply: file ends inside element %r (only triangle faces are read)' % name)
-            rows = np.frombuffer(data, dt, count, pos)
-            pos += count * dt.itemsize
-        if name == 'vertex':
-            for axis in 'xyz':
-                if axis not in dt.names:
-                    raise ValueError('read_ply: vertex property %r missing' % axis)
-            verts = np.stack([np.asarray(rows[a], np.float64) for a in 'xyz'], 1).reshape(-1, 3)
-            if all(a in dt.names for a in ('nx', 'ny', 'nz')):
-                normals = np.stack([np.asarray(rows[a], np.float64) for a in ('nx', 'ny', 'nz')], 1).reshape(-1, 3)
-        elif name == 'face':
-            lname = lists[0][0]
-            if count and not (np.asarray(rows[lname + '#n']) == 3).all():
-                raise ValueError('read_ply: only triangles are read')
-            faces = np.asarray(rows[lname]).astype(np.int64).reshape(-1, 3)
-    if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
-        raise ValueError('read_ply: face index out of range')
-    return Mesh(verts, faces, normals)

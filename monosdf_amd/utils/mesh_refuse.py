@@ -16,8 +16,10 @@ scores it (csrc/refuse.hip, ABI msdf_raster_* / msdf_tsdf_* / msdf_cull_*).
 All cameras are OpenCV-style: x right, y down, z forward, ``pose`` a 4x4 camera-to-world matrix (the frame the
 reference reaches after ``fix_pose`` and after cull_mesh.py's axis flips); ``K`` is (fx, fy, cx, cy) or a matrix with
 them at [0,0], [1,1], [0,2], [1,2].  Every pose is inverted on the host in fp64 and used in fp32.  Everything runs on
-CUDA tensors; there is no CPU path.  The same inputs give bitwise the same outputs every call (no floating-point
-atomics).  Not built: colour fusion (the reference fuses a constant white).
+CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function that takes a mesh
+validates it once (``mesh_tensors``) and hands it on to the unchecked ``_raster`` / ``_seen``.  The same inputs give
+bitwise the same outputs every call (no floating-point atomics).  Not built: colour fusion (the reference fuses a
+constant white).
 
 Parity with pyrender's rasteriser and with open3d's integration is UNVERIFIED: neither library is available where this
 is built and the reference holds no recorded output of them.  The pixel rule (a pixel's ray goes through its centre,
@@ -30,7 +32,7 @@ import re
 import numpy as np
 import torch
 
-from .. import _lib
+from . import mesh_args as ma
 from .mesh import Mesh, concatenate, marching_cubes
 
 
@@ -74,76 +76,12 @@ def _image_size(name, height, width):
     return h, w
 
 
-def _check_cuda(name, arg, t, dtypes, cols=3):
-    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
-        raise TypeError('%s: %s must be a CUDA tensor (there is no CPU path), got %s' %
-                        (name, arg, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-    if t.dtype not in dtypes:
-        raise TypeError('%s: %s must be %s, got %s' % (name, arg, ' or '.join(str(d) for d in dtypes), t.dtype))
-    if cols and (t.dim() != 2 or t.shape[1] != cols):
-        raise ValueError('%s: %s must be [N, %d], got %s' % (name, arg, cols, tuple(t.shape)))
-    if t.shape[0] >= 2 ** 31:
-        raise ValueError('%s: %s has %d rows: int32 indices hold fewer than 2^31' % (name, arg, t.shape[0]))
-
-
-def _check_mesh_tensors(name, vertices, faces):
-    """float32 [V,3] and int32 [F,3] contiguous CUDA tensors; ValueError for a face index outside [0, V) or a
-    non-finite coordinate (one device reduction and one host read)."""
-    _check_cuda(name, 'vertices', vertices, (torch.float32,))
-    _check_cuda(name, 'faces', faces, (torch.int32, torch.int64))
-    if faces.device != vertices.device:
-        raise ValueError('%s: vertices on %s, faces on %s' % (name, vertices.device, faces.device))
-    v = vertices.contiguous()
-    ok = torch.isfinite(v).all()
-    if faces.shape[0] > 0:
-        lo, hi = torch.aminmax(faces)
-        ok = torch.stack([ok, lo >= 0, hi < v.shape[0]])
-    if not bool(ok.all().item()):
-        if not bool(torch.isfinite(v).all().item()):
-            raise ValueError('%s: non-finite vertex coordinates' % name)
-        raise ValueError('%s: face index outside [0, %d)' % (name, v.shape[0]))
-    return v, faces.to(torch.int32).contiguous()
-
-
-def _host_mesh(name, mesh):
-    """A Mesh or a (vertices, faces) pair of numpy arrays, checked on the host -> (float64 [V,3], int64 [F,3],
-    normals or None); CUDA tensors pass through (checked later, on the device)."""
-    if isinstance(mesh, Mesh):
-        v, f, nrm = mesh.vertices, mesh.faces, mesh.vertex_normals
-    else:
-        v, f = mesh
-        nrm = None
-    if isinstance(v, torch.Tensor) or isinstance(f, torch.Tensor):
-        _check_cuda(name, 'vertices', v, (torch.float32,))
-        _check_cuda(name, 'faces', f, (torch.int32, torch.int64))
-        return v, f, None
-    v = np.asarray(v, dtype=np.float64)
-    f = np.asarray(f)
-    if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError('%s: vertices must be [V, 3], got %s' % (name, v.shape))
-    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
-        raise ValueError('%s: faces must be an integer [F, 3] array, got %s %s' % (name, f.dtype, f.shape))
-    if not np.isfinite(v).all():
-        raise ValueError('%s: non-finite vertex coordinates' % name)
-    if f.size and (f.min() < 0 or f.max() >= len(v)):
-        raise ValueError('%s: face index outside [0, %d)' % (name, len(v)))
-    return v, f.astype(np.int64), nrm
-
-
-def _upload(v, f):
-    if isinstance(v, torch.Tensor):
-        return v, f
-    return (torch.from_numpy(np.ascontiguousarray(v, np.float32)).cuda(),
-            torch.from_numpy(np.ascontiguousarray(f, np.int32)).cuda())
-
-
 def _raster(v, f, w2c, intr, h, w, znear, zfar, pixel_center):
     n = w2c.shape[0]
     depth = torch.empty(n, h, w, dtype=torch.float32, device=v.device)
     with torch.cuda.device(v.device):
-        _lib.call('msdf_raster_depth', _lib.ptr(v), v.shape[0], _lib.ptr(f), f.shape[0], _lib.ptr(w2c), n,
-                  intr[0], intr[1], intr[2], intr[3], h, w, float(znear), float(zfar), float(pixel_center),
-                  _lib.ptr(depth), _lib.stream_ptr())
+        ma.call('msdf_raster_depth', v, v.shape[0], f, f.shape[0], w2c, n, *intr, h, w, float(znear), float(zfar),
+                float(pixel_center), depth)
     return depth
 
 
@@ -160,15 +98,13 @@ def render_depth(vertices, faces, poses, K, height, width, znear=0.05, zfar=100.
     Parity with pyrender's rasteriser is UNVERIFIED (see the module's docstring): the half-pixel rule is OpenGL's.
     ValueError for a face index outside [0, V) and for non-finite coordinates or poses."""
     name = 'render_depth'
-    _check_cuda(name, 'vertices', vertices, (torch.float32,))
-    _check_cuda(name, 'faces', faces, (torch.int32, torch.int64))
     w2c = _world_to_camera(name, poses)
     intr = _intrinsics(name, K)
     h, w = _image_size(name, height, width)
     if not (float(znear) > 0.0 and float(zfar) >= float(znear) and np.isfinite(pixel_center)):
         raise ValueError('%s: 0 < znear <= zfar needed, got %r, %r' % (name, znear, zfar))
-    v, f = _check_mesh_tensors(name, vertices, faces)
-    return _raster(v, f, torch.from_numpy(w2c).to(v.device), intr, h, w, znear, zfar, pixel_center)
+    v, f, _ = ma.mesh_tensors(name, (vertices, faces))
+    return _raster(v, f, ma.upload(w2c, v.device), intr, h, w, znear, zfar, pixel_center)
 
 
 def _fusion_params(name, voxel_length, sdf_trunc, depth_trunc):
@@ -193,10 +129,8 @@ def _integrate(depth, w2c, intr, origin, offset, dims, vl, trunc, dtrunc, state=
     else:
         tsdf, weight = state
     with torch.cuda.device(dev):
-        _lib.call('msdf_tsdf_integrate', _lib.ptr(depth), _lib.ptr(w2c), depth.shape[0], intr[0], intr[1], intr[2],
-                  intr[3], depth.shape[1], depth.shape[2], origin[0], origin[1], origin[2], offset[0], offset[1],
-                  offset[2], nx, ny, nz, vl, trunc, dtrunc, 0 if state is None else 1, _lib.ptr(tsdf),
-                  _lib.ptr(weight), _lib.stream_ptr())
+        ma.call('msdf_tsdf_integrate', depth, w2c, depth.shape[0], *intr, depth.shape[1], depth.shape[2], *origin,
+                *offset, nx, ny, nz, vl, trunc, dtrunc, 0 if state is None else 1, tsdf, weight)
     return tsdf, weight
 
 
@@ -228,9 +162,7 @@ def tsdf_integrate(depth, poses, K, origin, dims, voxel_length, sdf_trunc, depth
     ``sdf_trunc`` None: 3 voxel_length.    One lane owns one voxel and applies the views in order: no atomics, bitwise reproducible.  The rule is written
     down from open3d's source; parity with open3d is UNVERIFIED (see the module's docstring)."""
     name = 'tsdf_integrate'
-    _check_cuda(name, 'depth', depth, (torch.float32,), cols=0)
-    if depth.dim() != 3:
-        raise ValueError('%s: depth must be [n, H, W], got %s' % (name, tuple(depth.shape)))
+    ma.check_tensor(name, 'depth', depth, shape='[n, H, W]')
     w2c = _world_to_camera(name, poses)
     if w2c.shape[0] != depth.shape[0]:
         raise ValueError('%s: %d depth maps, %d poses' % (name, depth.shape[0], w2c.shape[0]))
@@ -238,7 +170,7 @@ def tsdf_integrate(depth, poses, K, origin, dims, voxel_length, sdf_trunc, depth
     _image_size(name, depth.shape[1], depth.shape[2])
     vl, trunc, dtrunc = _fusion_params(name, voxel_length, sdf_trunc, depth_trunc)
     o, d, off = _grid_args(name, origin, dims, offset)
-    return _integrate(depth.contiguous(), torch.from_numpy(w2c).to(depth.device), intr, o, off, d, vl, trunc, dtrunc)
+    return _integrate(depth.contiguous(), ma.upload(w2c, depth.device), intr, o, off, d, vl, trunc, dtrunc)
 
 
 def tsdf_face_keep(vertices, faces, weight):
@@ -247,16 +179,16 @@ def tsdf_face_keep(vertices, faces, weight):
     ``weight > 0``.  For a face with area those are the 8 corners of its cell (open3d emits a cell's triangles only if
     all 8 corners were observed); for a face that lies in a cell face, that face's 4 corners."""
     name = 'tsdf_face_keep'
-    _check_cuda(name, 'vertices', vertices, (torch.float32,))
-    _check_cuda(name, 'faces', faces, (torch.int32,))
-    _check_cuda(name, 'weight', weight, (torch.float32,), cols=0)
-    if weight.dim() != 3 or weight.numel() == 0 or weight.numel() >= 2 ** 31:
+    ma.check_tensor(name, 'vertices', vertices, shape='[V, 3]')
+    ma.check_tensor(name, 'faces', faces, (torch.int32,), '[F, 3]')
+    ma.check_tensor(name, 'weight', weight, shape='[nx, ny, nz]')
+    if weight.numel() == 0 or weight.numel() >= 2 ** 31:
         raise ValueError('%s: weight must be [nx, ny, nz], got %s' % (name, tuple(weight.shape)))
+    dev = ma.same_device(name, vertices=vertices, faces=faces, weight=weight)
     v, f, wt = vertices.contiguous(), faces.contiguous(), weight.contiguous()
-    keep = torch.zeros(f.shape[0], dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.call('msdf_tsdf_face_keep', _lib.ptr(v), v.shape[0], _lib.ptr(f), f.shape[0], _lib.ptr(wt),
-                  wt.shape[0], wt.shape[1], wt.shape[2], _lib.ptr(keep), _lib.stream_ptr())
+    keep = torch.zeros(f.shape[0], dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        ma.call('msdf_tsdf_face_keep', v, v.shape[0], f, f.shape[0], wt, *wt.shape, keep)
     return keep.bool()
 
 
@@ -266,7 +198,7 @@ def extract_mesh(tsdf, weight, origin, voxel_length, offset=(0, 0, 0)):
     -> (vertices [V,3] float64 world = origin + voxel_length (0.5 + offset + v) (voxel_length as fp32), faces [F,3] int64, normals [V,3]
     float32), CUDA tensors.  Normals and winding point toward increasing tsdf: the free space in front of the surface."""
     name = 'extract_mesh'
-    _check_cuda(name, 'weight', weight, (torch.float32,), cols=0)
+    ma.check_tensor(name, 'weight', weight, shape='[nx, ny, nz]')
     if not isinstance(tsdf, torch.Tensor) or tsdf.shape != weight.shape or tsdf.device != weight.device:
         raise ValueError('%s: tsdf and weight must have one shape and device' % name)
     o = torch.tensor([float(x) for x in np.asarray(origin, np.float64).reshape(3)], dtype=torch.float64)
@@ -277,8 +209,7 @@ def extract_mesh(tsdf, weight, origin, voxel_length, offset=(0, 0, 0)):
         f = f[tsdf_face_keep(v, f, weight)].long()
         used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
         used[f.reshape(-1)] = True
-        new_index = torch.cumsum(used, 0) - 1
-        v, nrm, f = v[used], nrm[used], new_index[f]
+        v, nrm, f = v[used], nrm[used], ma.compact_faces(used, f, all_kept=True)
     else:
         f = f.long()
     world = (o + vl * (0.5 + off)).to(v.device) + vl * v.double()
@@ -333,12 +264,10 @@ def refuse(mesh, poses, K, height, width, voxel_length=0.01, sdf_trunc=None, dep
     chunk = n if view_chunk is None else int(view_chunk)
     if chunk < 1:
         raise ValueError('%s: view_chunk must be positive, got %r' % (name, view_chunk))
-    v, f, _ = _host_mesh(name, mesh)
-    v, f = _upload(v, f)
-    v, f = _check_mesh_tensors(name, v, f)
+    v, f, _ = ma.mesh_tensors(name, mesh)
     if v.shape[0] == 0 or f.shape[0] == 0:
         return concatenate([])
-    w2c = torch.from_numpy(w2c_h).to(v.device)
+    w2c = ma.upload(w2c_h, v.device)
     lo, hi = torch.aminmax(v, dim=0)
     origin, dims = fusion_grid(lo.double().cpu().numpy(), hi.double().cpu().numpy(), vl, trunc)
     origin32 = tuple(float(np.float32(x)) for x in origin)
@@ -367,16 +296,15 @@ def seen_vertices(vertices, poses, K, height, width):
     0 < fy p.y / (p.z - 1e-5) + cy < height (the test of replica_eval/cull_mesh.py:66-81 in the OpenCV frame; the
     1e-5 is the reference's).  One lane per vertex loops over the views and stops at the first that sees it."""
     name = 'seen_vertices'
-    _check_cuda(name, 'vertices', vertices, (torch.float32,))
-    w2c = _world_to_camera(name, poses)
-    intr = _intrinsics(name, K)
-    h, w = _image_size(name, height, width)
-    v = vertices.contiguous()
+    ma.check_tensor(name, 'vertices', vertices, shape='[V, 3]')
+    return _seen(vertices.contiguous(), _world_to_camera(name, poses), _intrinsics(name, K),
+                 *_image_size(name, height, width))
+
+
+def _seen(v, w2c, intr, h, w):
     seen = torch.zeros(v.shape[0], dtype=torch.uint8, device=v.device)
-    w2c = torch.from_numpy(w2c).to(v.device)
     with torch.cuda.device(v.device):
-        _lib.call('msdf_cull_vertices', _lib.ptr(v), v.shape[0], _lib.ptr(w2c), w2c.shape[0], intr[0], intr[1],
-                  intr[2], intr[3], h, w, _lib.ptr(seen), _lib.stream_ptr())
+        ma.call('msdf_cull_vertices', v, v.shape[0], ma.upload(w2c, v.device), w2c.shape[0], *intr, h, w, seen)
     return seen.bool()
 
 
@@ -386,18 +314,12 @@ def cull_to_frustums(mesh, poses, K, height, width):
     (``seen_vertices``) are dropped; the vertices all stay, as trimesh's ``update_faces`` leaves them.  ``mesh``: a Mesh
     or a (vertices, faces) pair (numpy arrays are uploaded; CUDA tensors: float32 / int32).  -> Mesh."""
     name = 'cull_to_frustums'
-    _world_to_camera(name, poses)
-    _intrinsics(name, K)
-    _image_size(name, height, width)
-    hv, hf, nrm = _host_mesh(name, mesh)
-    v, f = _upload(hv, hf)
-    v, f = _check_mesh_tensors(name, v, f)
-    seen = seen_vertices(v, poses, K, height, width)
+    w2c, intr, size = _world_to_camera(name, poses), _intrinsics(name, K), _image_size(name, height, width)
+    v, f, nrm = ma.mesh_tensors(name, mesh)
+    seen = _seen(v, w2c, intr, *size)
     keep = seen[f.long()].any(dim=1) if f.shape[0] > 0 else torch.zeros(0, dtype=torch.bool, device=v.device)
-    faces = f[keep].cpu().numpy()
-    if isinstance(hv, torch.Tensor):
-        return Mesh(hv.cpu().numpy(), faces)
-    return Mesh(hv, faces, nrm)
+    hv = ma.mesh_parts(mesh)[0]                        # the vertices all stay, host ones as they came (fp64)
+    return Mesh(v.cpu().numpy() if isinstance(hv, torch.Tensor) else hv, f[keep].cpu().numpy(), nrm)
 
 
 def read_poses(path, every=1):
