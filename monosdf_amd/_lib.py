@@ -14,32 +14,49 @@ MAX_LAYERS = 10
 MAX_TILES = 17
 
 
-class Layer(C.Structure):
+class _NoDict(type(C.Structure)):
+    def __new__(mcs, name, bases, namespace):
+        namespace.setdefault('__slots__', ())
+        return super().__new__(mcs, name, bases, namespace)
+
+
+class Struct(C.Structure, metaclass=_NoDict):
+    """Base of every mirror of a C struct.  Its instances have no __dict__, so assigning to a name that is no field
+    raises AttributeError (a plain ctypes.Structure would accept it and leave the field it was meant for zero)."""
+
+    def __reduce__(self):
+        # ctypes' own __reduce__ reads __dict__; as there, a struct that holds addresses is not copied or pickled
+        if any(ctype is C.c_void_p for _, ctype in self._fields_):
+            raise ValueError('monosdf_amd: %s holds addresses and cannot be copied or pickled' % type(self).__name__)
+        return type(self).from_buffer_copy, (bytes(self),)
+
+
+class Layer(Struct):
     _fields_ = [(n, C.c_int32) for n in
                 ('kt', 'ot', 'wf_off', 'wb_off', 'bias_off', 'skip_tile', 'hpre', 'qpre', 'abpre',
                  'ktp', 'otp', 'pad_')]
 
 
-class Plan(C.Structure):
+class Plan(Struct):
     _fields_ = [(n, C.c_int32) for n in
                 ('n_layers', 'e_tiles', 'aux_tiles', 'n_freqs', 'sdf_slot', 'feat_tiles', 'hsum',
                  'qsum', 'absum', 'wsdf_off', 'mode', 'out_act', 'precision', 'out_rows')] + [('layer', Layer * MAX_LAYERS)]
 
 
-class PackRule(C.Structure):
+class PackRule(Struct):
     _fields_ = [('w_off', C.c_int32), ('b_off', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32),
                 ('rowmap_off', C.c_int32), ('colmap_off', C.c_int32), ('scale', C.c_float),
                 ('pad_', C.c_int32)]
 
 
-class WgradItem(C.Structure):
+class WgradItem(Struct):
     _fields_ = [('x', C.c_int64), ('y', C.c_int64), ('v', C.c_int64),
                 ('part_off', C.c_int64), ('colsum_off', C.c_int64), ('vrow_off', C.c_int64),
                 ('x_ld', C.c_int32), ('y_ld', C.c_int32), ('wx', C.c_int32), ('wy', C.c_int32),
                 ('n_splits', C.c_int32), ('bufs', C.c_int32)]
 
 
-class ReduceRule(C.Structure):
+class ReduceRule(Struct):
     _fields_ = [('part_off', C.c_int64), ('dst_off', C.c_int64), ('n_blocks', C.c_int32),
                 ('wx', C.c_int32), ('wy', C.c_int32), ('rowmap_off', C.c_int32),
                 ('colmap_off', C.c_int32), ('dst_ld', C.c_int32), ('fixed_row', C.c_int32),
@@ -49,7 +66,7 @@ class ReduceRule(C.Structure):
 _P = C.c_void_p
 
 
-class FgArgs(C.Structure):
+class FgArgs(Struct):
     _fields_ = [('wpack', _P), ('bpack', _P), ('x', _P), ('aux', _P),
                 ('P', C.c_int32), ('P_pad', C.c_int32), ('n_clamp', C.c_int32), ('n_feat', C.c_int32),
                 ('clamp_radius', C.c_float), ('sphere_scale', C.c_float),
@@ -60,7 +77,7 @@ class FgArgs(C.Structure):
                 ('wg_first', C.c_int32)]
 
 
-class BwArgs(C.Structure):
+class BwArgs(Struct):
     _fields_ = [('wpack', _P), ('bpack', _P), ('x', _P),
                 ('P', C.c_int32), ('P_pad', C.c_int32), ('n_feat', C.c_int32), ('n_split', C.c_int32),
                 ('g_sdf', _P), ('g_feat', _P), ('g_nrm', _P), ('g_raux', _P), ('clamped', _P),
@@ -70,19 +87,19 @@ class BwArgs(C.Structure):
                 ('row_map', _P)]
 
 
-class ColorFwdArgs(C.Structure):
+class ColorFwdArgs(Struct):
     _fields_ = [('wpack', _P), ('bpack', _P), ('x', _P), ('dirs', _P), ('nrm', _P), ('feat', _P),
                 ('code', _P), ('P', C.c_int32), ('P_pad', C.c_int32), ('spr', C.c_int32),
                 ('save', C.c_int32), ('rgb', _P), ('H', _P), ('MISC', _P)]
 
 
-class ColorBwdArgs(C.Structure):
+class ColorBwdArgs(Struct):
     _fields_ = [('wpack', _P), ('bpack', _P), ('rgb', _P), ('g_rgb', _P),
                 ('P', C.c_int32), ('P_pad', C.c_int32), ('H', _P), ('AB', _P), ('g_feat', _P),
                 ('g_misc', _P), ('g_nrm', _P)]
 
 
-class CompositeArgs(C.Structure):
+class CompositeArgs(Struct):
     _fields_ = [('z', _P), ('sdf', _P), ('rgb', _P), ('nrm', _P), ('beta', _P), ('depth_scale', _P),
                 ('N', C.c_int32), ('S', C.c_int32), ('white_bkgd', C.c_int32),
                 ('bg0', C.c_float), ('bg1', C.c_float), ('bg2', C.c_float),
@@ -91,7 +108,7 @@ class CompositeArgs(C.Structure):
                 ('depth_vals', _P)]
 
 
-class CompositeBwdArgs(C.Structure):
+class CompositeBwdArgs(Struct):
     _fields_ = [('z', _P), ('sdf', _P), ('rgb', _P), ('nrm', _P), ('beta', _P), ('depth_scale', _P),
                 ('weights', _P), ('wsum', _P), ('depth_values', _P), ('g_rgb_values', _P),
                 ('g_depth', _P), ('g_normal', _P), ('g_weights', _P),
@@ -101,18 +118,18 @@ class CompositeBwdArgs(C.Structure):
                 ('pose', _P), ('pose_stride', C.c_int32), ('depth_scale_stride', C.c_int32)]
 
 
-class WnLayer(C.Structure):
+class WnLayer(Struct):
     _fields_ = [('v', _P), ('g', _P), ('b', _P), ('rows', C.c_int32), ('cols', C.c_int32),
                 ('w_off', C.c_int32), ('b_off', C.c_int32), ('row_off', C.c_int32), ('has_g', C.c_int32)]
 
 
-class ProbeLossArgs(C.Structure):
+class ProbeLossArgs(Struct):
     _fields_ = [('rgb', _P), ('nrm', _P), ('depth', _P), ('g1', _P), ('g2', _P), ('N', C.c_int32), ('M', C.c_int32),
                 ('w_normal', C.c_float), ('w_depth', C.c_float), ('w_eik', C.c_float), ('w_smooth', C.c_float),
                 ('g_rgb', _P), ('g_nrm', _P), ('g_depth', _P), ('g_g1', _P), ('g_g2', _P), ('partial', _P)]
 
 
-class MonoSdfLossArgs(C.Structure):
+class MonoSdfLossArgs(Struct):
     _fields_ = [(n, _P) for n in ('rgb', 'depth', 'normal', 'sdf', 'grad_theta', 'grad_nei', 'rgb_gt', 'depth_gt',
                                   'normal_gt', 'mask_gt')] + \
                [(n, C.c_int32) for n in ('N', 'S', 'E', 'gamma', 'scale_invariant')] + \
@@ -120,7 +137,7 @@ class MonoSdfLossArgs(C.Structure):
                [(n, _P) for n in ('mask', 'out', 'g_rgb', 'g_depth', 'g_normal', 'g_theta', 'g_nei')]
 
 
-class SamplerArgs(C.Structure):
+class SamplerArgs(Struct):
     _fields_ = [('ray_o', _P), ('ray_d', _P), ('N', C.c_int32), ('M', C.c_int32), ('m_max', C.c_int32),
                 ('n_eval', C.c_int32), ('n_final', C.c_int32), ('n_extra', C.c_int32),
                 ('round_idx', C.c_int32), ('max_rounds', C.c_int32), ('training', C.c_int32),
@@ -288,3 +305,66 @@ def addr(t):
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class Binder:
+    """One struct of the ABI, filled by field name -- the only way this package fills an argument struct or a record.
+
+    Named: a name that is no field of the struct raises, and so does `pad_`.  Complete: launch() and bytes() raise
+    until every field but `pad_` has been given at least once, so NULL pointers and zero scalars are written out
+    (None, 0).  Kind-checked: a pointer field takes a tensor (its data_ptr()), None (NULL) or a Python int (an address:
+    a workspace region, a run flag); a scalar field takes a number and neither a tensor nor None.  Owning: `held` maps
+    every pointer field to what was bound to it, so a bound tensor lives as long as this object.  Device, dtype and
+    contiguity of a tensor are the caller's business (some fields are read through strided views on purpose)."""
+
+    _pointer = {}            # struct class -> {field: whether it is a pointer}, without pad_
+
+    def __init__(self, struct, **fields):
+        if struct not in self._pointer:
+            self._pointer[struct] = {n: t is C.c_void_p for n, t in struct._fields_ if n != 'pad_'}
+        self.struct, self.held = struct(), {}
+        self._kinds = self._pointer[struct]
+        self._unnamed = set(self._kinds)
+        self._ref = C.byref(self.struct)
+        self.bind(**fields)
+
+    def bind(self, **fields):
+        """Give fields their values; a field may be given again."""
+        kinds, struct, held = self._kinds, self.struct, self.held
+        for name, value in fields.items():
+            pointer = kinds.get(name)
+            if pointer is None:
+                raise AttributeError('monosdf_amd: %s has no field %r that can be given' % (type(struct).__name__, name))
+            if pointer:
+                if hasattr(value, 'data_ptr'):
+                    address = value.data_ptr()
+                elif value is None or type(value) is int:
+                    address = value
+                else:
+                    raise TypeError('monosdf_amd: %s.%s is a pointer: it takes a tensor, None or an address, not %r'
+                                    % (type(struct).__name__, name, value))
+                held[name], value = value, address
+            elif value is None or hasattr(value, 'data_ptr'):
+                raise TypeError('monosdf_amd: %s.%s is a scalar: it takes a number, not %s'
+                                % (type(struct).__name__, name, 'None' if value is None else 'a tensor'))
+            setattr(struct, name, value)
+        self._unnamed.difference_update(fields)
+
+    def complete(self):
+        """The struct, once every field has been named."""
+        if self._unnamed:
+            raise RuntimeError('monosdf_amd: %s with fields never given: %s'
+                               % (type(self.struct).__name__, ', '.join(sorted(self._unnamed))))
+        return self.struct
+
+    def __bytes__(self):
+        return bytes(self.complete())
+
+    def launch(self, entry, plan=None, stream=None):
+        """call(entry, [byref(plan),] byref(struct), stream); stream: a stream_ptr() taken earlier (default: now)."""
+        self.complete()
+        stream = stream_ptr() if stream is None else stream
+        if plan is None:
+            call(entry, self._ref, stream)
+        else:
+            call(entry, C.byref(plan), self._ref, stream)

@@ -7,7 +7,6 @@ device: the kernels of a round return at once when the previous round did not as
 enqueue rounds without reading the flags back (``speculate``), and only has to check afterwards that it
 enqueued enough of them."""
 import collections
-import ctypes as C
 import math
 
 import torch
@@ -59,22 +58,16 @@ SUPPLIED = ('ray_o', 'ray_d', 'beta0', 'new_sdf', 'jitter', 'u_final', 'extra_id
 LEFT_NULL = ('dbg_dstar', 'dbg_err0', 'dbg_cdf', 'rounds_out')
 
 
-class _SamplerCall:
-    """The msdf_sampler_args_t of one call and every tensor whose address sits in it: they live as long as this does."""
+class _SamplerCall(_lib.Binder):
+    """The msdf_sampler_args_t of one call and every tensor whose address sits in it: they live as long as this does.
+    A call is filled in stages: every pointer field starts out NULL, the scalars of a round 0, and bind() gives them
+    their values as the call goes on."""
 
     def __init__(self, sizes, device, **scalars):
-        self.sizes, self.device, self.held, self.stream = sizes, device, {}, _lib.stream_ptr()
-        a = self.args = _lib.SamplerArgs()
-        a.N, a.n_eval, a.n_final, a.n_extra = sizes.N, sizes.n_eval, sizes.n_final, sizes.n_extra
-        a.max_rounds, a.m_max, a.training = sizes.K, sizes.n_eval * sizes.K, int(sizes.training)
-        for name, value in scalars.items():
-            setattr(a, name, value)
-
-    def bind(self, **tensors):
-        """Pointer fields from tensors (None -> NULL)."""
-        for name, t in tensors.items():
-            setattr(self.args, name, _lib.addr(t))
-            self.held[name] = t
+        self.sizes, self.device, self.stream = sizes, device, _lib.stream_ptr()
+        super().__init__(_lib.SamplerArgs, N=sizes.N, n_eval=sizes.n_eval, n_final=sizes.n_final, n_extra=sizes.n_extra,
+                         max_rounds=sizes.K, m_max=sizes.n_eval * sizes.K, training=int(sizes.training), M=0,
+                         round_idx=0, eik_unit=0, **dict.fromkeys((*ALLOCATED, *SUPPLIED, *LEFT_NULL)), **scalars)
 
     def alloc(self, *names):
         """The call's own buffers, from the table, bound; returns them in the order asked for."""
@@ -87,7 +80,7 @@ class _SamplerCall:
         return list(new.values())
 
     def launch(self, entry):
-        _lib.call(entry, C.byref(self.args), self.stream)
+        super().launch(entry, stream=self.stream)
 
 
 class UniformSampler(RaySampler):
@@ -110,7 +103,7 @@ class UniformSampler(RaySampler):
         # the first step of an error-bound call of one round with no final set: its n_eval samples are the result
         bound = float(self.scene_bounding_sphere) if self.take_sphere_intersection else 0.0
         call = _SamplerCall(_Sizes(N, n, 0, 0, 1, False, False), dev, near=float(self.near), far=float(self.far),
-                            bound=bound, lemma=1.0)
+                            bound=bound, lemma=1.0, beta_iters=0, eps=0.0, add_tiny=0.0)
         call.bind(ray_o=cam_loc, ray_d=ray_dirs, jitter=None if jitter is None else _need_gpu(jitter))
         z, far = call.alloc('z', 'far_out')
         call.alloc('new_z', 'new_pos', 'pts', 'beta')        # msdf_sampler_init writes them too: not returned
@@ -322,8 +315,8 @@ class ErrorBoundSampler(RaySampler):
         # fused forward kernel on the new points, [N*n_eval, 1]; in a speculated round it returns at once when the
         # previous round did not ask for this one
         run_flag = flags.data_ptr() + 4 * (2 * k - 1) if (speculate > 0 and k > 0) else None
-        call.bind(new_sdf=net._sdf_only(pts, run_flag=run_flag, save_for=save_for))
-        call.args.M, call.args.round_idx = call.sizes.n_eval * (k + 1), k
+        call.bind(new_sdf=net._sdf_only(pts, run_flag=run_flag, save_for=save_for), M=call.sizes.n_eval * (k + 1),
+                  round_idx=k)
         call.launch('msdf_sampler_beta')
         group = self.global_rounds
         if group is not None:
@@ -356,8 +349,9 @@ class ErrorBoundSampler(RaySampler):
         call = _SamplerCall(d, dev, beta_iters=self.beta_iters, near=float(self.near), far=float(self.far),
                             bound=float(self.scene_bounding_sphere), eps=float(self.eps),
                             add_tiny=float(self.add_tiny), lemma=self._lemma)
-        draws, call.args.eik_unit = self._draws(noise, d, dev) if d.training else ({}, False)
-        call.bind(ray_o=cam_loc, ray_d=ray_dirs, beta0=beta0, jitter=draws.get('jitter'), u_final=draws.get('final_u'))
+        draws, eik_unit = self._draws(noise, d, dev) if d.training else ({}, False)
+        call.bind(ray_o=cam_loc, ray_d=ray_dirs, beta0=beta0, jitter=draws.get('jitter'), u_final=draws.get('final_u'),
+                  eik_unit=eik_unit)
         pts, flags = call.alloc('pts', 'flags')
         call.alloc('z', 'sdf', 'new_z', 'new_pos', 'beta', 'final_z')
         extra_idx = save_for = None

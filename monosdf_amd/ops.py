@@ -183,18 +183,13 @@ class WeightNormTables:
         dev = tensors[0].device
         recs, row_layer, w_off, b_off, it = [], [], 0, 0, iter(tensors)
         for i, (rows, cols, has_g) in enumerate(shapes):
-            r = _lib.WnLayer()
-            v = next(it)
-            g = next(it) if has_g else None
-            b = next(it)
-            r.v, r.g, r.b = v.data_ptr(), _lib.addr(g), b.data_ptr()
-            r.rows, r.cols = rows, cols
-            r.w_off, r.b_off, r.row_off, r.has_g = w_off, b_off, b_off, int(has_g)
-            recs.append(bytes(r))
+            recs.append(_lib.Binder(_lib.WnLayer, v=next(it), g=next(it) if has_g else None, b=next(it), rows=rows,
+                                    cols=cols, w_off=w_off, b_off=b_off, row_off=b_off, has_g=int(has_g)))
             row_layer += [i] * rows
             w_off += rows * cols
             b_off += rows
-        self.layers_dev = torch.from_numpy(np.frombuffer(b''.join(recs), dtype=np.uint8).copy()).to(dev)
+        self.params = tuple(tensors)   # the parameters whose addresses the device table names
+        self.layers_dev = torch.from_numpy(np.frombuffer(b''.join(map(bytes, recs)), dtype=np.uint8).copy()).to(dev)
         self.row_layer_dev = torch.tensor(row_layer, dtype=torch.int32, device=dev)
         self.n_w, self.total_rows = w_off, b_off
 
@@ -279,6 +274,11 @@ REUSE_SAMPLER_H = _os.environ.get('MSDF_REUSE_SAMPLER_H', '1') != '0'
 # (shorter) ones first, instead of rotated so that they start last (msdf_fg_args_t.wg_first).  Bit-identical
 # either way (tests/test_gpu_fg_dispatch_order.py): for comparisons.
 FG_REUSE_LAST = _os.environ.get('MSDF_FG_REUSE_LAST', '1') != '0'
+
+
+# the field groups of msdf_fg_args_t / msdf_bw_args_t that are present or absent together, absent
+_NO_JACOBIAN = dict(dy_dx=None, aux_dx_scale=0.0)
+_NO_REUSE = dict(row_map=None, n_reuse=0, smp_flags=None, h_saved=None, h_stage=None, stage_pad=0, wg_first=0)
 
 
 def _fg_wg_first(reuse):
@@ -402,31 +402,20 @@ def _sdf_fwd_grad(x, aux, wpack, bpack, mlp, n_clamp, n_feat, clamp_radius, sphe
     aux_shape = (aLC // aC, P, aC) if aC else (P, 16 * plan.aux_tiles)
     r_aux = torch.empty(*aux_shape, device=dev, dtype=torch.float32) if has_aux else None
     clamped = torch.empty(max(P, 1), device=dev, dtype=torch.uint8)
-    a = _lib.FgArgs()
-    a.wpack, a.bpack, a.x, a.aux = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr(), _lib.addr(aux)
-    a.P, a.P_pad, a.n_clamp, a.n_feat = P, P_pad, n_clamp, n_feat
-    a.clamp_radius, a.sphere_scale = float(clamp_radius), float(sphere_scale)
-    a.sdf, a.feat, a.nrm, a.r_aux, a.clamped = sdf.data_ptr(), feat.data_ptr(), nrm.data_ptr(), _lib.addr(r_aux), \
-        clamped.data_ptr()
-    base = ws.data_ptr()
-    a.H = base + 4 * woff['H']
-    a.PM = base + 4 * woff['PM'] if save else None
-    a.IN0 = base + 4 * woff['IN0'] if save else None
-    a.save = 1 if save else 0
-    a.aux_C, a.aux_LC = int(aC), int(aLC)
-    jac_scale = None
-    if aux_jac is not None and aC == 2:
-        jac_scale = float(aux_jac[1])
-        a.dy_dx, a.aux_dx_scale = aux_jac[0].data_ptr(), jac_scale
-    saved = (x, ws, clamped, wpack, bpack)
-    if reuse is not None:
-        a.row_map, a.n_reuse = reuse.row_map.data_ptr(), reuse.n_reuse
-        a.smp_flags, a.h_saved = reuse.flags.data_ptr(), reuse.h_saved.data_ptr()
-        a.h_stage, a.stage_pad = _lib.addr(reuse.stage), reuse.stage_pad
-        a.wg_first = _fg_wg_first(reuse)
-        saved += (reuse.row_map,)
+    jac_scale = float(aux_jac[1]) if (aux_jac is not None and aC == 2) else None
+    jac = _NO_JACOBIAN if jac_scale is None else dict(dy_dx=aux_jac[0], aux_dx_scale=jac_scale)
+    shared = _NO_REUSE if reuse is None else dict(
+        row_map=reuse.row_map, n_reuse=reuse.n_reuse, smp_flags=reuse.flags, h_saved=reuse.h_saved,
+        h_stage=reuse.stage, stage_pad=reuse.stage_pad, wg_first=_fg_wg_first(reuse))
+    a = _lib.Binder(_lib.FgArgs, wpack=wpack, bpack=bpack, x=x, aux=aux, P=P, P_pad=P_pad, n_clamp=n_clamp,
+                    n_feat=n_feat, clamp_radius=float(clamp_radius), sphere_scale=float(sphere_scale), sdf=sdf,
+                    feat=feat, nrm=nrm, r_aux=r_aux, clamped=clamped, H=planlib.region(ws, woff, 'H'),
+                    PM=planlib.region(ws, woff, 'PM') if save else None,
+                    IN0=planlib.region(ws, woff, 'IN0') if save else None, save=1 if save else 0, aux_C=int(aC),
+                    aux_LC=int(aLC), **jac, **shared)
+    saved = (x, ws, clamped, wpack, bpack) + (() if reuse is None else (reuse.row_map,))
     if P > 0:
-        _lib.call('msdf_sdf_fwd_grad', C.byref(plan), C.byref(a), _lib.stream_ptr())
+        a.launch('msdf_sdf_fwd_grad', plan)
     ns = P if n_split is None else int(n_split)
     state = _SdfState(mlp, P, P_pad, n_feat, ns, save, has_aux, (int(aC), int(aLC)), aux_shape, jac_scale)
     return (sdf[:ns], sdf[ns:], feat, nrm[:ns], nrm[ns:], r_aux), saved, state
@@ -447,23 +436,18 @@ def _sdf_backward(state, saved, grads, dy_dx=None, gg_out=None, after_sweeps=Non
     woff, _ = planlib.sdf_workspace(mp, P_pad)
     g_sdf, g_sdf_b, g_feat, g_nrm, g_nrm_b, g_raux = [_cont(g) for g in grads]
     g_aux = torch.empty(*state.aux_shape, device=dev, dtype=torch.float32) if state.has_aux else None
-    b = _lib.BwArgs()
-    b.aux_C, b.aux_LC = state.aux_lm
-    if state.jac_scale is not None:
-        b.dy_dx, b.aux_dx_scale, b.gg_out = dy_dx.data_ptr(), state.jac_scale, _lib.addr(gg_out)
-    b.wpack, b.bpack, b.x = wpack.data_ptr(), bpack.data_ptr(), x.data_ptr()
-    b.P, b.P_pad, b.n_feat, b.n_split = P, P_pad, state.n_feat, state.n_split
-    b.g_sdf, b.g_sdf_b, b.g_nrm, b.g_nrm_b = _lib.addr(g_sdf), _lib.addr(g_sdf_b), _lib.addr(g_nrm), _lib.addr(g_nrm_b)
-    b.g_feat = _lib.addr(g_feat) if state.n_feat > 0 else None
-    b.g_raux = _lib.addr(g_raux) if state.has_aux else None
-    b.clamped = clamped.data_ptr()
-    b.row_map = row_map[0].data_ptr() if row_map else None
-    base = ws.data_ptr()
-    for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST'):
-        setattr(b, k, base + 4 * woff[k])
-    b.g_aux = _lib.addr(g_aux)
+    if state.jac_scale is not None and dy_dx is None:
+        raise RuntimeError('monosdf_amd: the forward launch applied the encoder\'s Jacobian, the backward needs dy_dx')
+    jac = _NO_JACOBIAN if state.jac_scale is None else dict(dy_dx=dy_dx, aux_dx_scale=state.jac_scale)
+    b = _lib.Binder(_lib.BwArgs, wpack=wpack, bpack=bpack, x=x, P=P, P_pad=P_pad, n_feat=state.n_feat,
+                    n_split=state.n_split, g_sdf=g_sdf, g_sdf_b=g_sdf_b, g_nrm=g_nrm, g_nrm_b=g_nrm_b,
+                    g_feat=g_feat if state.n_feat > 0 else None, g_raux=g_raux if state.has_aux else None,
+                    clamped=clamped, row_map=row_map[0] if row_map else None, T=None, g_aux=g_aux,
+                    aux_C=state.aux_lm[0], aux_LC=state.aux_lm[1],
+                    gg_out=gg_out if state.jac_scale is not None else None, **jac,
+                    **{k: planlib.region(ws, woff, k) for k in ('H', 'PM', 'QB', 'AB', 'GSDF', 'QLAST')})
     if P > 0:
-        _lib.call('msdf_sdf_backward', C.byref(mlp.plan), C.byref(b), _lib.stream_ptr())
+        b.launch('msdf_sdf_backward', mlp.plan)
         start_side_work(dev)                 # the colour network's queued weight-gradient launch, if any
     if after_sweeps is not None:
         after_sweeps(g_aux)
@@ -657,17 +641,12 @@ class ColorMlpFunction(torch.autograd.Function):
         woff, total = planlib.color_workspace(mp, P_pad)
         ws = torch.empty(max(total if save else 64, 64), device=dev, dtype=torch.float32)
         rgb = torch.empty(P, 3, device=dev, dtype=torch.float32)
-        a = _lib.ColorFwdArgs()
-        a.wpack, a.bpack = wpack.data_ptr(), bpack.data_ptr()
-        a.x, a.dirs, a.nrm, a.feat = x.data_ptr(), dirs.data_ptr(), nrm.data_ptr(), feat.data_ptr()
-        a.code = _lib.addr(code) if has_code else None
-        a.P, a.P_pad, a.spr, a.save = P, P_pad, int(spr), 1 if save else 0
-        a.rgb = rgb.data_ptr()
-        base = ws.data_ptr()
-        a.H = base + 4 * woff['H'] if save else None
-        a.MISC = base + 4 * woff['MISC'] if save else None
+        a = _lib.Binder(_lib.ColorFwdArgs, wpack=wpack, bpack=bpack, x=x, dirs=dirs, nrm=nrm, feat=feat,
+                        code=code if has_code else None, P=P, P_pad=P_pad, spr=int(spr), save=1 if save else 0, rgb=rgb,
+                        H=planlib.region(ws, woff, 'H') if save else None,
+                        MISC=planlib.region(ws, woff, 'MISC') if save else None)
         if P > 0:
-            _lib.call('msdf_color_forward', C.byref(plan), C.byref(a), _lib.stream_ptr())
+            a.launch('msdf_color_forward', plan)
         ctx.cmlp, ctx.P, ctx.P_pad, ctx.saved, ctx.has_code, ctx.spr = cmlp, P, P_pad, save, has_code, spr
         ctx.save_for_backward(rgb, feat, ws, wpack, bpack)
         return rgb
@@ -686,16 +665,12 @@ class ColorMlpFunction(torch.autograd.Function):
         g_rgb = g_rgb.contiguous()
         g_feat = torch.empty_like(feat)
         g_misc = torch.empty(P, 16 * mp.misc_tiles, device=dev, dtype=torch.float32)
-        b = _lib.ColorBwdArgs()
-        b.wpack, b.bpack, b.rgb, b.g_rgb = wpack.data_ptr(), bpack.data_ptr(), rgb.data_ptr(), g_rgb.data_ptr()
-        b.P, b.P_pad = P, P_pad
-        base = ws.data_ptr()
-        b.H, b.AB = base + 4 * woff['H'], base + 4 * woff['AB']
-        b.g_feat, b.g_misc = g_feat.data_ptr(), g_misc.data_ptr()
         g_nrm = torch.empty(P, 3, device=dev, dtype=torch.float32) if plan.mode == 1 else None
-        b.g_nrm = _lib.addr(g_nrm)
+        b = _lib.Binder(_lib.ColorBwdArgs, wpack=wpack, bpack=bpack, rgb=rgb, g_rgb=g_rgb, P=P, P_pad=P_pad,
+                        H=planlib.region(ws, woff, 'H'), AB=planlib.region(ws, woff, 'AB'), g_feat=g_feat,
+                        g_misc=g_misc, g_nrm=g_nrm)
         if P > 0:
-            _lib.call('msdf_color_backward', C.byref(plan), C.byref(b), _lib.stream_ptr())
+            b.launch('msdf_color_backward', plan)
             grad = cmlp.run_wgrad(P_pad, {'ws': ws, 'feat': feat}, defer=USE_SIDE_STREAM)
             if USE_SIDE_STREAM and COLOR_WGRAD_EARLY:
                 # start it now: it then runs beside the SDF backward kernel and fills the partly filled last round
@@ -750,27 +725,22 @@ class CompositeFunction(torch.autograd.Function):
         normal_map = torch.empty(N, 3, device=dev)
         wsum = torch.empty(max(N, 1), device=dev)
         depth_vals = torch.empty(N, S, device=dev) if want_depth_vals else None
-        a = _lib.CompositeArgs()
-        a.z, a.sdf, a.rgb, a.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
-        a.beta, a.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
-        a.depth_scale_stride = ds_stride
-        a.depth_vals = _lib.addr(depth_vals)
-        a.N, a.S, a.white_bkgd = N, S, 1 if white_bkgd else 0
-        a.bg0, a.bg1, a.bg2 = [float(v) for v in bg]
-        a.weights, a.rgb_values, a.depth_values = weights.data_ptr(), rgb_values.data_ptr(), depth_values.data_ptr()
-        a.normal_map, a.wsum = normal_map.data_ptr(), wsum.data_ptr()
-        if pose is not None:
+        ctx.has_pose = pose is not None
+        if ctx.has_pose:
             pose = _need_cuda(pose.detach(), 'pose').reshape(-1, 4, 4)
             if pose.shape[0] not in (1, N):
                 raise RuntimeError('monosdf_amd: pose must be [1,4,4] or [N,4,4]')
-            a.pose, a.pose_stride = pose.data_ptr(), (16 if pose.shape[0] == N and N > 1 else 0)
+            ctx.pose_stride = 16 if pose.shape[0] == N and N > 1 else 0
         else:
-            pose = z.new_zeros(1)
-            a.pose, a.pose_stride = None, 0
-        ctx.has_pose, ctx.pose_stride = a.pose is not None, a.pose_stride
-        _lib.call('msdf_composite_forward', C.byref(a), _lib.stream_ptr())
+            pose, ctx.pose_stride = z.new_zeros(1), 0
+        bg = [float(v) for v in bg]
+        _lib.Binder(_lib.CompositeArgs, z=z, sdf=sdf, rgb=rgb, nrm=nrm, beta=beta, depth_scale=depth_scale,
+                    depth_scale_stride=ds_stride, depth_vals=depth_vals, N=N, S=S, white_bkgd=1 if white_bkgd else 0,
+                    bg0=bg[0], bg1=bg[1], bg2=bg[2], weights=weights, rgb_values=rgb_values, depth_values=depth_values,
+                    normal_map=normal_map, wsum=wsum, pose=pose if ctx.has_pose else None,
+                    pose_stride=ctx.pose_stride).launch('msdf_composite_forward')
         ctx.save_for_backward(z, sdf, rgb, nrm, beta, depth_scale, weights, wsum, depth_values, pose, raw)
-        ctx.white_bkgd, ctx.bg, ctx.ds_stride = white_bkgd, [float(v) for v in bg], ds_stride
+        ctx.white_bkgd, ctx.bg, ctx.ds_stride = white_bkgd, bg, ds_stride
         if want_depth_vals:
             ctx.mark_non_differentiable(depth_vals)       # z_vals carries no gradient (the sampler runs under no_grad)
             return weights, rgb_values, depth_values, normal_map, depth_vals
@@ -787,19 +757,12 @@ class CompositeFunction(torch.autograd.Function):
         g_rgb = torch.empty(N, S, 3, device=dev)
         g_nrm = torch.empty(N, S, 3, device=dev)
         g_beta_part = torch.empty(max(N, 1), device=dev)
-        b = _lib.CompositeBwdArgs()
-        b.z, b.sdf, b.rgb, b.nrm = z.data_ptr(), sdf.data_ptr(), rgb.data_ptr(), nrm.data_ptr()
-        b.beta, b.depth_scale = beta.data_ptr(), depth_scale.data_ptr()
-        b.weights, b.wsum, b.depth_values = weights.data_ptr(), wsum.data_ptr(), depth_values.data_ptr()
-        b.g_rgb_values, b.g_depth = _lib.addr(g_rgbv), _lib.addr(g_depth)
-        b.g_normal, b.g_weights = _lib.addr(g_nmap), _lib.addr(g_w)
-        b.N, b.S, b.white_bkgd = N, S, 1 if ctx.white_bkgd else 0
-        b.bg0, b.bg1, b.bg2 = ctx.bg
-        b.g_sdf, b.g_rgb, b.g_nrm, b.g_beta_part = g_sdf.data_ptr(), g_rgb.data_ptr(), g_nrm.data_ptr(), \
-            g_beta_part.data_ptr()
-        b.pose, b.pose_stride = (pose.data_ptr() if ctx.has_pose else None), ctx.pose_stride
-        b.depth_scale_stride = ctx.ds_stride
-        _lib.call('msdf_composite_backward', C.byref(b), _lib.stream_ptr())
+        _lib.Binder(_lib.CompositeBwdArgs, z=z, sdf=sdf, rgb=rgb, nrm=nrm, beta=beta, depth_scale=depth_scale,
+                    weights=weights, wsum=wsum, depth_values=depth_values, g_rgb_values=g_rgbv, g_depth=g_depth,
+                    g_normal=g_nmap, g_weights=g_w, N=N, S=S, white_bkgd=1 if ctx.white_bkgd else 0, bg0=ctx.bg[0],
+                    bg1=ctx.bg[1], bg2=ctx.bg[2], g_sdf=g_sdf, g_rgb=g_rgb, g_nrm=g_nrm, g_beta_part=g_beta_part,
+                    pose=pose if ctx.has_pose else None, pose_stride=ctx.pose_stride,
+                    depth_scale_stride=ctx.ds_stride).launch('msdf_composite_backward')
         sh = ctx.in_shapes
         if ctx.beta_shape is not None:
             # d loss / d beta_raw = sign(beta_raw) * sum over rays, one launch (fixed summation order)
@@ -1005,13 +968,9 @@ class ProbeLossFunction(torch.autograd.Function):
         dev = rgb.device
         flat, outs = _flat_grad_views((rgb, nrm, depth, g1, g2))
         partial = torch.empty(1, device=dev, dtype=torch.float32)        # the complete loss value (one workgroup)
-        a = _lib.ProbeLossArgs()
-        a.rgb, a.nrm, a.depth, a.g1, a.g2 = [t.data_ptr() for t in (rgb, nrm, depth, g1, g2)]
-        a.N, a.M = N, M
-        a.w_normal, a.w_depth, a.w_eik, a.w_smooth = float(w_normal), float(w_depth), float(w_eik), float(w_smooth)
-        a.g_rgb, a.g_nrm, a.g_depth, a.g_g1, a.g_g2 = [t.data_ptr() for t in outs]
-        a.partial = partial.data_ptr()
-        _lib.call('msdf_probe_loss', C.byref(a), _lib.stream_ptr())
+        _lib.Binder(_lib.ProbeLossArgs, rgb=rgb, nrm=nrm, depth=depth, g1=g1, g2=g2, N=N, M=M, w_normal=float(w_normal),
+                    w_depth=float(w_depth), w_eik=float(w_eik), w_smooth=float(w_smooth), g_rgb=outs[0], g_nrm=outs[1],
+                    g_depth=outs[2], g_g1=outs[3], g_g2=outs[4], partial=partial).launch('msdf_probe_loss')
         ctx.save_for_backward(flat)
         ctx.shapes = [t.shape for t in outs]
         return partial.reshape(())
@@ -1080,18 +1039,14 @@ class MonoSdfLossFunction(torch.autograd.Function):
         out = torch.empty(8, device=dev, dtype=torch.float32)
         mask = torch.empty(N, device=dev, dtype=torch.float32)
         flat, grads = _flat_grad_views([rgb, depth, normal] + ([g1, g2] if has_eik else []))
-        a = _lib.MonoSdfLossArgs()
-        a.rgb, a.depth, a.normal, a.sdf = rgb.data_ptr(), depth.data_ptr(), normal.data_ptr(), sdf.data_ptr()
-        a.rgb_gt, a.depth_gt, a.normal_gt, a.mask_gt = [t.data_ptr() for t in data]
-        a.N, a.S, a.E = N, sdf.shape[1], (g1.shape[0] if has_eik else 0)
-        a.gamma, a.scale_invariant = int(bool(gamma)), int(bool(scale_invariant))
-        a.w_eik, a.w_smooth, a.w_depth, a.w_nl1, a.w_ncos = [float(w) for w in weights]
-        a.mask, a.out = mask.data_ptr(), out.data_ptr()
-        a.g_rgb, a.g_depth, a.g_normal = [t.data_ptr() for t in grads[:3]]
-        if has_eik:
-            a.grad_theta, a.grad_nei = g1.data_ptr(), g2.data_ptr()
-            a.g_theta, a.g_nei = grads[3].data_ptr(), grads[4].data_ptr()
-        _lib.call('msdf_monosdf_loss', C.byref(a), _lib.stream_ptr())
+        eik = (g1, g2, grads[3], grads[4]) if has_eik else (None,) * 4
+        w_eik, w_smooth, w_depth, w_nl1, w_ncos = map(float, weights)
+        _lib.Binder(_lib.MonoSdfLossArgs, rgb=rgb, depth=depth, normal=normal, sdf=sdf, grad_theta=eik[0], grad_nei=eik[1],
+                    rgb_gt=data[0], depth_gt=data[1], normal_gt=data[2], mask_gt=data[3], N=N, S=sdf.shape[1],
+                    E=g1.shape[0] if has_eik else 0, gamma=int(bool(gamma)), scale_invariant=int(bool(scale_invariant)),
+                    w_eik=w_eik, w_smooth=w_smooth, w_depth=w_depth, w_nl1=w_nl1, w_ncos=w_ncos, mask=mask, out=out,
+                    g_rgb=grads[0], g_depth=grads[1], g_normal=grads[2], g_theta=eik[2],
+                    g_nei=eik[3]).launch('msdf_monosdf_loss')
         ctx.has_eik = has_eik
         ctx.save_for_backward(flat)
         ctx.shapes = [t.shape for t in grads]

@@ -257,27 +257,31 @@ def build_color_plan(w_shapes, mode, n_freqs_view, feature_size, code_cols=0, ou
 # ---------------------------------------------------------------------------
 # workspace layouts (float offsets for a given P_pad)
 # ---------------------------------------------------------------------------
-def sdf_workspace(mp, P_pad):
-    P = mp.plan
-    n = P.n_layers
-    sizes = [('H', P.hsum * P_pad), ('PM', P.hsum * P_pad), ('IN0', 16 * mp.in0_tiles * P_pad),
-             ('QB', P.qsum * P_pad), ('AB', P.absum * P_pad),
-             ('GSDF', P_pad), ('QLAST', 16 * P.layer[n - 1].kt * P_pad)]
+def _layout(sizes):
+    """Regions of the given float counts, one behind the other, each starting at a multiple of 64 floats."""
     off, total = {}, 0
     for k, s in sizes:
         off[k] = total
         total += (s + 63) & ~63
     return off, total
+
+
+def sdf_workspace(mp, P_pad):
+    P = mp.plan
+    n = P.n_layers
+    return _layout([('H', P.hsum * P_pad), ('PM', P.hsum * P_pad), ('IN0', 16 * mp.in0_tiles * P_pad),
+                    ('QB', P.qsum * P_pad), ('AB', P.absum * P_pad),
+                    ('GSDF', P_pad), ('QLAST', 16 * P.layer[n - 1].kt * P_pad)])
 
 
 def color_workspace(mp, P_pad):
     P = mp.plan
-    sizes = [('H', P.hsum * P_pad), ('MISC', 16 * mp.misc_tiles * P_pad), ('AB', P.absum * P_pad)]
-    off, total = {}, 0
-    for k, s in sizes:
-        off[k] = total
-        total += (s + 63) & ~63
-    return off, total
+    return _layout([('H', P.hsum * P_pad), ('MISC', 16 * mp.misc_tiles * P_pad), ('AB', P.absum * P_pad)])
+
+
+def region(ws, off, name):
+    """Device address of region `name` of the float32 workspace tensor `ws` laid out by `off`."""
+    return ws.data_ptr() + 4 * off[name]
 
 
 # ---------------------------------------------------------------------------

@@ -34,27 +34,226 @@ def test_library_exports_every_declared_symbol():
     assert lib.msdf_abi_version() == _lib.ABI_VERSION == 8
 
 
-def test_struct_sizes_match_header():
-    """ctypes mirrors of the C structs must have the C compiler's layout."""
-    import subprocess, tempfile
+def _mirrors():
+    """C struct name -> its ctypes mirror: all fifteen structs of the ABI."""
     from monosdf_amd import _lib
-    names = {'msdf_plan_t': _lib.Plan, 'msdf_layer_t': _lib.Layer, 'msdf_packrule_t': _lib.PackRule,
-             'msdf_wgrad_item_t': _lib.WgradItem, 'msdf_reduce_rule_t': _lib.ReduceRule,
-             'msdf_fg_args_t': _lib.FgArgs, 'msdf_bw_args_t': _lib.BwArgs,
-             'msdf_color_fwd_args_t': _lib.ColorFwdArgs, 'msdf_color_bwd_args_t': _lib.ColorBwdArgs,
-             'msdf_composite_args_t': _lib.CompositeArgs, 'msdf_composite_bwd_args_t': _lib.CompositeBwdArgs,
-             'msdf_sampler_args_t': _lib.SamplerArgs, 'msdf_wn_layer_t': _lib.WnLayer,
-             'msdf_probe_loss_args_t': _lib.ProbeLossArgs, 'msdf_monosdf_loss_args_t': _lib.MonoSdfLossArgs}
-    src = '#include <stdio.h>\n#include "monosdf_hip.h"\nint main(){' + ''.join(
-        'printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in names) + 'return 0;}'
+    return {'msdf_plan_t': _lib.Plan, 'msdf_layer_t': _lib.Layer, 'msdf_packrule_t': _lib.PackRule,
+            'msdf_wgrad_item_t': _lib.WgradItem, 'msdf_reduce_rule_t': _lib.ReduceRule,
+            'msdf_fg_args_t': _lib.FgArgs, 'msdf_bw_args_t': _lib.BwArgs,
+            'msdf_color_fwd_args_t': _lib.ColorFwdArgs, 'msdf_color_bwd_args_t': _lib.ColorBwdArgs,
+            'msdf_composite_args_t': _lib.CompositeArgs, 'msdf_composite_bwd_args_t': _lib.CompositeBwdArgs,
+            'msdf_sampler_args_t': _lib.SamplerArgs, 'msdf_wn_layer_t': _lib.WnLayer,
+            'msdf_probe_loss_args_t': _lib.ProbeLossArgs, 'msdf_monosdf_loss_args_t': _lib.MonoSdfLossArgs}
+
+
+def test_struct_layouts_match_header():
+    """ctypes mirrors of the C structs must have the C compiler's layout: the size of every struct, and the offset and
+    size of every field (two swapped fields of one width keep the struct's size)."""
+    import subprocess, tempfile
+    names = _mirrors()
+    fields = [(n, f) for n, cls in names.items() for f, _ in cls._fields_]
+    assert len(names) == 15 and len(fields) == 288
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "monosdf_hip.h"\nint main(){' + ''.join(
+        'printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in names) + ''.join(
+        'printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (n, f, n, f, n, f)
+        for n, f in fields) + 'return 0;}'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, 't.c'), 'w').write(src)
         subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), os.path.join(d, 't.c'), '-o',
                                os.path.join(d, 't')])
-        out = subprocess.check_output([os.path.join(d, 't')]).decode().split()
-    sizes = dict(zip(out[::2], map(int, out[1::2])))
+        out = [l.split() for l in subprocess.check_output([os.path.join(d, 't')]).decode().splitlines()]
+    c_side = {l[0]: tuple(map(int, l[1:])) for l in out}
+    assert len(c_side) == len(names) + len(fields)
     for n, cls in names.items():
-        assert ctypes.sizeof(cls) == sizes[n], (n, ctypes.sizeof(cls), sizes[n])
+        assert (ctypes.sizeof(cls),) == c_side[n], (n, ctypes.sizeof(cls), c_side[n])
+    for n, f in fields:
+        desc = getattr(names[n], f)
+        assert (desc.offset, desc.size) == c_side[n + '.' + f], (n, f, desc.offset, desc.size, c_side[n + '.' + f])
+
+
+_C_SCALARS = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'uint32_t': ctypes.c_uint32, 'int64_t': ctypes.c_int64,
+              'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
+# entry points that take a struct pointer as an opaque address: a table in device memory
+_DEVICE_TABLES = {'msdf_pack_weights', 'msdf_weightnorm_forward', 'msdf_weightnorm_backward', 'msdf_wgrad',
+                  'msdf_reduce'}
+
+
+def _prototypes():
+    """(return type, name, parameter text) of every prototype of the header, comments stripped."""
+    text = open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
+
+
+def test_prototypes_match_the_binding():
+    """Every prototype of the header against _lib._SIGNATURES: the number of arguments, the ctypes type of each and
+    the rule for the return type."""
+    from monosdf_amd import _lib
+    assert ctypes.c_int is ctypes.c_int32
+    protos = _prototypes()
+    assert len(protos) == 64 and sorted(p[1] for p in protos) == _lib.exported_symbols()
+    mirrors, tables = _mirrors(), set()
+    for ret, name, params in protos:
+        params = [p.split() for p in params.replace('*', ' * ').split(',')]
+        params = [] if params == [['void']] else params
+        expected = []
+        for i, words in enumerate(params):
+            words = [w for w in words[:-1] if w != 'const']        # the last word is the parameter's name
+            if words[-1] != '*':
+                assert len(words) == 1, (name, i, words)
+                expected.append((_C_SCALARS[words[0]],))
+            elif words[0] in mirrors:
+                assert len(words) == 2, (name, i, words)
+                expected.append((ctypes.POINTER(mirrors[words[0]]), ctypes.c_void_p))
+            else:
+                assert not words[0].startswith('msdf_'), (name, i, words)      # T*, T* const*: an address
+                expected.append((ctypes.c_void_p,))
+        bound = _lib._SIGNATURES[name]
+        assert len(bound) == len(expected), (name, len(bound), len(expected))
+        for i, (have, want) in enumerate(zip(bound, expected)):
+            assert have in want, (name, i, have, want)
+            if have is ctypes.c_void_p and len(want) == 2:
+                tables.add(name)
+    assert tables == _DEVICE_TABLES
+    for ret, name, _ in protos:                # the rule by which load() chooses the return type
+        assert (ret == 'int64_t') == name.endswith('_bytes'), name
+
+
+def test_loaded_library_has_the_header_return_types():
+    """What load() set on the functions of the library: the header's return type, _SIGNATURES' arguments."""
+    from monosdf_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip('library not built (run python __graft_entry__.py)')
+    lib = _lib.load()
+    protos = _prototypes()
+    assert len(protos) == 64
+    for ret, name, _ in protos:
+        assert getattr(lib, name).restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
+        assert getattr(lib, name).argtypes == _lib._SIGNATURES[name], name
+
+
+def test_every_mirror_refuses_an_unknown_field():
+    from monosdf_amd import _lib
+    for name, cls in _mirrors().items():
+        with pytest.raises(AttributeError, match=cls.__name__):
+            cls().no_such_field = 1
+    with pytest.raises(AttributeError, match='Layer'):
+        _lib.Plan().layer[3].no_such_field = 1
+
+
+def test_plans_and_weight_norm_tables_copy_and_pickle():
+    """What a module keeps after its first forward -- plan, pack rules, weight-gradient program, weight-norm tables --
+    deep-copies and pickles (copy.deepcopy / torch.save of a model that has run); a struct of addresses does neither."""
+    import copy
+    import pickle
+    from monosdf_amd import _lib, ops, plan as planlib
+    mp = planlib.build_sdf_plan([(64, 39), (64, 64), (65, 64)], [], 6, 0, False, 64)
+    prog = planlib.balanced_program(planlib.build_sdf_wgrad, mp, 128)
+    for clone in (copy.deepcopy, lambda o: pickle.loads(pickle.dumps(o))):
+        mp2, prog2 = clone(mp), copy.deepcopy(prog)
+        assert bytes(mp2.plan) == bytes(mp.plan) and any(bytes(mp.plan)) and mp2.plan is not mp.plan
+        assert bytes(mp2.plan.layer[1]) == bytes(mp.plan.layer[1]) == bytes(clone(mp.plan.layer[1]))
+        assert [bytes(r) for r in mp2.rules] == [bytes(r) for r in mp.rules] and mp.rules
+        assert bytes(mp2.build_b16(2)) == bytes(mp.build_b16(2))
+        assert prog2.rules_bytes().tobytes() == prog.rules_bytes().tobytes()
+        assert prog2.items_bytes().tobytes() == prog.items_bytes().tobytes()
+        mp2.plan.n_layers += 1                                    # a copy, not a view
+        assert mp2.plan.n_layers == mp.plan.n_layers + 1
+    params = [torch.zeros(4, 3), torch.ones(4, 1), torch.zeros(4), torch.zeros(2, 4), torch.zeros(2)]
+    state = ops.WeightNormState()
+    tables = state.tables(((4, 3, True), (2, 4, False)), params)
+    assert all(a is b for a, b in zip(tables.params, params)) and tables.total_rows == 6 and tables.n_w == 20
+    recs = bytes(tables.layers_dev.numpy())
+    assert len(recs) == 2 * ctypes.sizeof(_lib.WnLayer)
+    first = _lib.WnLayer.from_buffer_copy(recs[:ctypes.sizeof(_lib.WnLayer)])
+    assert (first.v, first.g, first.b, first.has_g) == (params[0].data_ptr(), params[1].data_ptr(), params[2].data_ptr(), 1)
+    for clone in (copy.deepcopy, lambda o: pickle.loads(pickle.dumps(o))):
+        state2 = clone(state)
+        assert torch.equal(state2.cur.layers_dev, tables.layers_dev) and state2.key == state.key
+        assert [p.shape for p in state2.cur.params] == [p.shape for p in params]
+        assert state2.cur.params[0].data_ptr() != params[0].data_ptr()
+        # the copy rebuilds its table for the copied parameters, as it does when a parameter moves
+        copied = state2.cur
+        assert state2.tables(((4, 3, True), (2, 4, False)), copied.params) is not copied
+    for clone in (copy.deepcopy, pickle.dumps):
+        with pytest.raises(ValueError, match='WnLayer'):
+            clone(first)
+
+
+# the structs that hold addresses: filled through _lib.Binder alone inside the package
+_BOUND = ('FgArgs', 'BwArgs', 'ColorFwdArgs', 'ColorBwdArgs', 'CompositeArgs', 'CompositeBwdArgs', 'ProbeLossArgs',
+          'MonoSdfLossArgs', 'SamplerArgs', 'WnLayer')
+
+
+def _binder_values(cls):
+    """One value per field but pad_: tensors, a NULL and an address for the pointers, ints and floats for the scalars."""
+    values = {}
+    for i, (name, ctype) in enumerate(f for f in cls._fields_ if f[0] != 'pad_'):
+        if ctype is ctypes.c_void_p:
+            values[name] = (None, 4096 + 64 * i, torch.zeros(3))[min(i % 5, 2)]
+        else:
+            values[name] = 0.25 * i if ctype is ctypes.c_float else 3 + i
+    return values
+
+
+@pytest.mark.parametrize('struct', _BOUND)
+def test_binder_fills_a_struct_like_hand_assignment(struct, monkeypatch):
+    import gc
+    import weakref
+    from monosdf_amd import _lib
+    cls = getattr(_lib, struct)
+    values = _binder_values(cls)
+    tensors = [v for v in values.values() if torch.is_tensor(v)]
+    assert set(values) == {n for n, _ in cls._fields_} - {'pad_'} and tensors
+    by_hand = cls()
+    for name, v in values.items():
+        setattr(by_hand, name, v.data_ptr() if torch.is_tensor(v) else v)
+    bound = _lib.Binder(cls, **values)
+    assert bytes(bound) == bytes(by_hand) == bytes(bound.struct) and any(bytes(by_hand))
+    # in stages, and given again: the last value holds
+    first = next(iter(values))
+    staged = _lib.Binder(cls, **{first: values[first]})
+    other = {n: (None if t is ctypes.c_void_p else 1) for n, t in cls._fields_ if n != 'pad_'}
+    staged.bind(**other)
+    staged.bind(**values)
+    assert bytes(staged) == bytes(by_hand)
+    # the launch: call(entry, [byref(plan),] byref(struct), stream)
+    calls = []
+    monkeypatch.setattr(_lib, 'call', lambda *a: calls.append(a))
+    plan = _lib.Plan()
+    bound.launch('msdf_entry', stream='s0')
+    bound.launch('msdf_entry', plan, stream='s1')
+    assert [(c[0], len(c), c[-1]) for c in calls] == [('msdf_entry', 3, 's0'), ('msdf_entry', 4, 's1')]
+    assert calls[0][1]._obj is bound.struct and calls[1][2]._obj is bound.struct and calls[1][1]._obj is plan
+    # what is refused, by field name
+    a_scalar = next(n for n, t in cls._fields_ if t is not ctypes.c_void_p and n != 'pad_')
+    a_pointer = next(n for n, t in cls._fields_ if t is ctypes.c_void_p)
+    for bad, error in (({'no_such_field': 1}, AttributeError), ({'pad_': 0}, AttributeError),
+                       ({a_scalar: tensors[0]}, TypeError), ({a_scalar: None}, TypeError),
+                       ({a_pointer: 1.5}, TypeError)):
+        with pytest.raises(error, match=r'%s\b.*\b%s\b' % (struct, next(iter(bad)))):
+            _lib.Binder(cls, **bad)
+        with pytest.raises(error, match=next(iter(bad))):
+            bound.bind(**bad)
+    assert bytes(bound) == bytes(by_hand)
+    for missing in (a_scalar, a_pointer):
+        short = _lib.Binder(cls, **{n: v for n, v in values.items() if n != missing})
+        with pytest.raises(RuntimeError, match=r'%s\b.*: %s$' % (struct, missing)):
+            short.launch('msdf_entry', stream='s2')
+        with pytest.raises(RuntimeError, match=missing):
+            bytes(short)
+    assert len(calls) == 2
+    # a bound tensor lives exactly as long as the binder
+    name = next(n for n, v in values.items() if torch.is_tensor(v))
+    alive = weakref.ref(values[name])
+    del values, tensors, v, short
+    staged.bind(**{name: None})
+    gc.collect()
+    assert alive() is not None and alive() is bound.held[name] and alive().data_ptr() == getattr(bound.struct, name)
+    del bound
+    gc.collect()
+    assert alive() is None
 
 
 def test_sampler_call_table_names_every_pointer_field():
@@ -185,6 +384,23 @@ def test_sdf_plan_slot_maps_reproduce_the_network(kind, width):
     for l in range(P.n_layers):
         L = P.layer[l]
         assert L.ktp >= L.kt and L.otp >= L.ot and L.kt <= 17 and L.ot <= 17
+
+
+def test_workspace_regions_follow_one_layout():
+    """Both workspaces: regions in the stated order, each at a multiple of 64 floats, none overlapping the next;
+    plan.region() is the byte address of a region inside the workspace tensor."""
+    from monosdf_amd import plan as planlib
+    sdf = planlib.build_sdf_plan([(64, 39), (64, 64), (65, 64)], [], 6, 0, False, 64)
+    col = planlib.build_color_plan([(64, 97), (64, 64), (3, 64)], 'idr', 4, 64)
+    for mp, layout, order in ((sdf, planlib.sdf_workspace, ['H', 'PM', 'IN0', 'QB', 'AB', 'GSDF', 'QLAST']),
+                              (col, planlib.color_workspace, ['H', 'MISC', 'AB'])):
+        off, total = layout(mp, 192)
+        starts = [off[k] for k in order] + [total]
+        assert list(off) == order and starts[0] == 0 and starts == sorted(starts)
+        assert all(s % 64 == 0 for s in starts) and len(set(starts)) == len(starts)
+        assert off[order[1]] == mp.plan.hsum * 192                      # H: hsum floats per point, 192 = 3 * 64 points
+        ws = torch.zeros(total)
+        assert [planlib.region(ws, off, k) - ws.data_ptr() for k in order] == [4 * off[k] for k in order]
 
 
 def test_wgrad_program_covers_every_weight_once():
