@@ -239,6 +239,17 @@ _SIGNATURES = {
 
 ABI_VERSION = 8
 
+# The entry points of include/monosdf_gridnn.h (csrc/gridnn.hip): additive, outside the versioned table above and its
+# header; load() binds both tables by the same rule.
+_GRIDNN_SIGNATURES = {
+    'msdf_gnn_workspace_bytes': [C.c_int64],
+    'msdf_gnn_cells': [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P,
+                       _P],
+    'msdf_gnn_records': [_P, _P, C.c_int64, _P, _P],
+    'msdf_gnn_query': [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                       C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P],
+}
+
 _lib = None
 
 
@@ -252,7 +263,7 @@ def load():
             'monosdf_amd: %s not found -- build it with `python __graft_entry__.py` or '
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()):
         fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int

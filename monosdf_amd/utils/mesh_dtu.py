@@ -1,5 +1,6 @@
 """The DTU evaluation protocol on the GPU: the reference's dtu_eval/evaluate_single_scene.py (``cull_scan``) and
-dtu_eval/eval.py (csrc/dtueval.hip, ABI msdf_dtu_*; the closing distance queries are ``mesh_eval.nearest_neighbors``).
+dtu_eval/eval.py (csrc/dtueval.hip, ABI msdf_dtu_*; the closing distance queries are ``mesh_eval.nearest_neighbors``
+or, with ``search='grid'``, the grid-bounded ``mesh_eval.nearest_neighbors_within``).
 
 * ``dilate_masks``: skimage's ``binary_dilation(mask, disk(12))`` of every view's object mask
   (evaluate_single_scene.py:80-82), all views in one launch on bit-packed rows.
@@ -14,8 +15,10 @@ dtu_eval/eval.py (csrc/dtueval.hip, ABI msdf_dtu_*; the closing distance queries
 Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function
 that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_lattice``.  Every rule is
 integer, boolean, separately rounded fp32 or fp64, with no floating-point atomics: the same inputs give bitwise the
-same outputs every call, and the numpy restatements of tests/dtu_numpy.py are matched exactly.  Not built: the two
-coloured error clouds ``vis_*_d2s.ply`` / ``vis_*_s2d.ply`` that eval.py also writes.
+same outputs every call, and the numpy restatements of tests/dtu_numpy.py are matched exactly.  The two closing queries
+take nearly all of the protocol's time by brute force; ``evaluate_dtu(..., search='grid')`` gives the same metrics through
+the search bounded by ``max_dist``.  Not built: the two coloured error clouds ``vis_*_d2s.ply`` / ``vis_*_s2d.ply`` that
+eval.py also writes.
 """
 import glob
 import os
@@ -25,7 +28,7 @@ import torch
 
 from . import mesh_args as ma
 from .mesh import Mesh, read_ply
-from .mesh_eval import nearest_neighbors
+from .mesh_eval import nearest_neighbors, nearest_neighbors_within
 
 MAX_RADIUS = 32                      # pixels: the dilation kernel reads a word and its two neighbours
 _CELL_AXIS_MAX = 2 ** 21             # cells per axis the 63-bit cell key holds
@@ -249,7 +252,7 @@ def _mean_below(dist, max_dist):
 
 @torch.no_grad()
 def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0.2, patch=60, max_dist=20, seed=0,
-                 order=None, return_clouds=False):
+                 order=None, return_clouds=False, search='brute'):
     """dtu_eval/eval.py from the sampling on.  ``mesh_or_points``: a Mesh or a (vertices, faces) pair (the reference's
     mesh mode) or a bare [N,3] cloud (its pcd mode), in the DTU world frame (millimetres); ``stl_points`` [S,3] the
     scan's reference cloud; ``obs_mask`` [X,Y,Z] (non-zero = observed), ``bb`` [2,3] and ``res`` from
@@ -264,8 +267,15 @@ def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0
     'd2s': the mean distance from data_in_obs to the stl cloud over the distances < max_dist; 's2d': the mean distance
     from ``stl_above``, the stl points with plane . (x, 1) > 0, to data_in (not data_in_obs), likewise; 'overall':
     their mean.  -> a dict of Python floats (nan where no distance is below max_dist).  ``return_clouds``: also a dict
-    with 'data_pcd', 'order', 'keep', 'data_in', 'data_in_obs', 'stl_above', 'dist_d2s', 'dist_s2d' (tensors)."""
+    with 'data_pcd', 'order', 'keep', 'data_in', 'data_in_obs', 'stl_above', 'dist_d2s', 'dist_s2d' (tensors).
+
+    ``search``: 'brute' (the default) sends the two closing queries through ``nearest_neighbors``; 'grid' sends them
+    through ``nearest_neighbors_within(..., max_dist)``, which needs ``max_dist`` positive and finite.  The distances
+    below ``max_dist`` are the same bits in the same order, so the three metrics are equal as Python floats; with
+    'grid', 'dist_d2s' and 'dist_s2d' hold +inf wherever the brute-force distance exceeds ``max_dist``."""
     name = 'evaluate_dtu'
+    if search not in ('brute', 'grid'):
+        raise ValueError("%s: search must be 'brute' or 'grid', got %r" % (name, search))
     dev = ma.device_of(stl_points, obs_mask)
     if isinstance(mesh_or_points, (tuple, list)) or hasattr(mesh_or_points, 'faces'):
         v, f, _ = ma.mesh_tensors(name, mesh_or_points, dev)
@@ -307,12 +317,17 @@ def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0
     data_in_obs = data_in[grid_in][in_obs]
     if stl.shape[0] == 0:
         raise ValueError('%s: the stl cloud is empty' % name)
-    dist_d2s = nearest_neighbors(stl, data_in_obs)[0]
+    if search == 'grid':
+        def nearest(reference, query):
+            return nearest_neighbors_within(reference, query, max_dist)
+    else:
+        nearest = nearest_neighbors
+    dist_d2s = nearest(stl, data_in_obs)[0]
     s64 = stl.double()
     above = ((s64[:, 0] * pl[0] + s64[:, 1] * pl[1]) + s64[:, 2] * pl[2]) + pl[3] > 0
     stl_above = stl[above]
     if data_in.shape[0] > 0:
-        dist_s2d = nearest_neighbors(data_in, stl_above)[0]
+        dist_s2d = nearest(data_in, stl_above)[0]
     else:
         dist_s2d = torch.full((stl_above.shape[0],), float('inf'), dtype=torch.float32, device=dev)
     d2s, s2d = _mean_below(dist_d2s, max_dist), _mean_below(dist_s2d, max_dist)

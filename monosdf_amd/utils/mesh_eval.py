@@ -3,6 +3,9 @@
 * ``nearest_neighbors``: exact brute-force 1-nearest-neighbour search (csrc/nnsearch.hip, ABI msdf_nn_*), in place of
   sklearn's ``KDTree(...).query`` (scannet_eval/evaluate.py:16-26) and scipy's ``cKDTree(...).query``
   (replica_eval/eval_recon.py:25-43, 96-106).
+* ``nearest_neighbors_within``: the same answer, bit for bit, for the queries that have a reference point within
+  ``max_dist``, through a uniform grid (csrc/gridnn.hip, ABI msdf_gnn_* of include/monosdf_gridnn.h): the search of the
+  DTU protocol's two closing queries, which use only the distances below ``max_dist``.
 * ``voxel_down_sample``: the rule of open3d's ``PointCloud.voxel_down_sample`` (evaluate.py:36-38; ABI msdf_voxel_*).
 * ``sample_surface``, ``face_normals``: trimesh.sample.sample_surface and Trimesh.face_normals (eval_recon.py:138-158).
 * ``evaluate_scannet``: ``evaluate`` (evaluate.py:29-56).  ``evaluate_replica``: the metrics of ``calc_3d_metric``
@@ -12,8 +15,9 @@
 Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function
 that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_face_cross``.
 Out of scope: ICP alignment (``get_align_transformation``), the oriented-bounding-box crop of ``calc_3d_metric``
-(eval_recon.py:121-136), and any grid- or tree-accelerated search: brute force is the exact baseline a later one is
-checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to the predicted mesh
+(eval_recon.py:121-136), and an unbounded grid- or tree-accelerated search: the means of the ScanNet and Replica
+protocols need every distance, their brute-force searches take milliseconds, and brute force is the exact baseline
+that ``nearest_neighbors_within`` is checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to the predicted mesh
 before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol and its mask culling are in
 utils/mesh_dtu.py.
 """
@@ -49,6 +53,97 @@ def nearest_neighbors(reference, query, n_splits=0):
         with torch.cuda.device(dev):
             ws = ma.workspace(name, 'msdf_nn_workspace_bytes', R, Q, int(n_splits), device=dev)
             ma.call('msdf_nn_search', ref, R, qry, Q, int(n_splits), ws, dist, idx)
+    return dist, idx.long()
+
+
+GRID_CELL_FRACTION = 16              # default cell side: max_dist over this (the best of the sweep of DESIGN 4.12)
+GRID_MAX_CELLS = 2 ** 25             # default cap of the cell count: a start table of 128 MiB (unmeasured)
+_GRID_CELLS_LIMIT = 2 ** 31 - 2      # the start table is indexed in int32
+
+
+def _positive(name, arg, value):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: %s must be a number, got %r' % (name, arg, value))
+    if not (v > 0.0 and np.isfinite(v)):
+        raise ValueError('%s: %s must be positive and finite, got %r' % (name, arg, value))
+    return v
+
+
+def grid_dims(lo, hi, h, max_cells):
+    """The grid of ``nearest_neighbors_within`` over the box lo..hi (three Python floats each): the cell side, ``h``
+    enlarged by steps of a quarter until the cell count fits ``max_cells``, and the cells per axis,
+    floor((hi - lo) / h) + 1 in fp64, the expression that gives a point its cell.  -> (h, (nx, ny, nz))"""
+    while True:
+        n = [np.floor((b - a) / h) + 1.0 for a, b in zip(lo, hi)]
+        if n[0] * n[1] * n[2] <= max_cells:
+            return h, tuple(int(c) for c in n)
+        h *= 1.25
+
+
+def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=None):
+    """``nearest_neighbors(reference, query)`` for the queries that have a reference point within ``max_dist``:
+    ``(dist [Q] float32, idx [Q] int64)``.  With (d, i) what ``nearest_neighbors`` returns for a query: bitwise (d, i)
+    if d <= float32(max_dist), else (+inf, -1).  reference [R,3], query [Q,3]: float32 CUDA tensors on one device.
+
+    Exact, through a uniform grid over the reference cloud's bounding box: the reference points are sorted by cell
+    (a stable ``torch.sort``), a dense table holds every cell's first point, and a query scans the cube of cells within
+    1, 2, 4, ... cells of its own until no point outside the cube can be as near as the best inside it, or the cube
+    reaches ``max_dist`` (csrc/gridnn.hip has the argument).  ``cell``: the cell side (default ``max_dist`` / 16);
+    ``max_cells``: the cap of the cell count (default 2^25), to which the cell side is enlarged.  Both change the speed
+    only: the result does not depend on them, and is bitwise the same every call (no atomics).  A query with no
+    neighbour within ``max_dist`` walks every cube up to that distance: the search is fast where most queries have a
+    near neighbour.  ValueError for an empty reference cloud, non-finite coordinates, a ``max_dist`` that is not
+    positive and finite (as a float32 too), and a ``cell`` or ``max_cells`` that is given and not positive."""
+    name = 'nearest_neighbors_within'
+    ma.check_tensor(name, 'reference', reference)
+    ma.check_tensor(name, 'query', query)
+    dev = ma.same_device(name, reference=reference, query=query)
+    md = _positive(name, 'max_dist', max_dist)
+    if md > float(np.finfo(np.float32).max):
+        raise ValueError('%s: max_dist must be finite as a float32, got %r' % (name, max_dist))
+    h = md / GRID_CELL_FRACTION if cell is None else _positive(name, 'cell', cell)
+    cap = GRID_MAX_CELLS if max_cells is None else _positive(name, 'max_cells', max_cells)
+    R, Q = reference.shape[0], query.shape[0]
+    if R == 0:
+        raise ValueError('%s: the reference cloud is empty' % name)
+    ref, qry = reference.contiguous(), query.contiguous()
+    _, lo_h, hi_h = ma.finite_bounds(name, ref)
+    if Q > 0 and not bool(torch.isfinite(qry).all().item()):
+        raise ValueError('%s: non-finite coordinates' % name)
+    if Q == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+    lo = lo_h.tolist()
+    h, dims = grid_dims(lo, hi_h.tolist(), h, max(1, int(min(cap, _GRID_CELLS_LIMIT))))
+    with torch.cuda.device(dev):
+        return _grid_query(qry, _grid_build(ref, (*lo, h, *dims)), md)
+
+
+def _grid_build(ref, grid):
+    """The reference cloud (checked, contiguous, on the current device) in the cells of ``grid`` = (lo_x, lo_y, lo_z,
+    h, nx, ny, nz): -> (grid, R, records, starts), the arguments of msdf_gnn_query."""
+    R, dev = ref.shape[0], ref.device
+    cells = torch.empty(R, dtype=torch.int32, device=dev)
+    ma.call('msdf_gnn_cells', ref, R, *grid, cells)
+    sorted_cells, order = torch.sort(cells, stable=True)
+    records = ma.workspace('nearest_neighbors_within', 'msdf_gnn_workspace_bytes', R, device=dev)
+    ma.call('msdf_gnn_records', ref, order, R, records)
+    every_cell = torch.arange(grid[4] * grid[5] * grid[6] + 1, dtype=torch.int32, device=dev)
+    return grid, R, records, torch.searchsorted(sorted_cells, every_cell, out_int32=True)
+
+
+def _grid_query(qry, built, max_dist):
+    """The answer of ``nearest_neighbors_within`` for the queries (checked, contiguous, at least one, on the current
+    device) against what ``_grid_build`` returned."""
+    grid, n_ref, records, starts = built
+    Q, dev = qry.shape[0], qry.device
+    cells = torch.empty(Q, dtype=torch.int32, device=dev)
+    ma.call('msdf_gnn_cells', qry, Q, *grid, cells)
+    order = torch.sort(cells, stable=True)[1]
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    idx = torch.empty(Q, dtype=torch.int32, device=dev)
+    ma.call('msdf_gnn_query', qry, order, Q, records, n_ref, starts, *grid, max_dist, dist, idx)
     return dist, idx.long()
 
 

@@ -2,13 +2,15 @@
 
     python scripts/eval_mesh.py PRED.ply GT.ply --protocol scannet|replica [--scale-mat cameras.npz]
     python scripts/eval_mesh.py PRED.ply --protocol dtu --dtu-dir DTU --scan 24 [--cameras cameras.npz --masks DIR|NPY]
+                                         [--search brute|grid]
 
 scannet: evaluate() of scannet_eval/evaluate.py (vertex clouds, 2 cm voxel down-sample, 5 cm threshold).
 replica: the metrics of calc_3d_metric() of replica_eval/eval_recon.py (200,000 surface samples per mesh, 5 cm).
 dtu: evaluate_single_scene.py + eval.py of dtu_eval (monosdf_amd/utils/mesh_dtu.py): with --cameras and --masks the mesh
 (in the normalised training frame) is first culled to the dilated object masks and taken to the world frame by
 `scale_mat_0`; without them PRED.ply must be culled and in the world frame already.  --dtu-dir holds the official
-ObsMask/ and Points/stl/ folders.  Prints d2s, s2d and their mean in millimetres.
+ObsMask/ and Points/stl/ folders.  Prints d2s, s2d and their mean in millimetres.  --search grid runs the two closing
+distance queries through the grid-bounded search (nearest_neighbors_within): the same numbers, sooner.
 --scale-mat: a cameras.npz whose `scale_mat_0` takes the predicted mesh from the normalised training frame to the
 world frame (evaluation/eval.py applies it before it writes the mesh; pass it when PRED.ply was written without).
 The meshes must be aligned already: ICP and the bounding-box crop are not done here (monosdf_amd/utils/mesh_eval.py).
@@ -40,7 +42,7 @@ def evaluate_dtu(ap, args):
         pred.apply_transform(np.load(args.scale_mat)['scale_mat_0'])
     scene = mesh_dtu.read_dtu_scene(args.dtu_dir, args.scan)
     return mesh_dtu.evaluate_dtu(pred, scene['stl_points'], scene['obs_mask'], scene['bb'], scene['res'],
-                                 scene['plane'], density=args.density, seed=args.seed)
+                                 scene['plane'], density=args.density, seed=args.seed, search=args.search)
 
 
 def main():
@@ -53,6 +55,8 @@ def main():
     ap.add_argument('--cameras', default=None, help='dtu: the scene\'s cameras.npz, for the mask cull')
     ap.add_argument('--masks', default=None, help='dtu: the scene\'s mask directory or an .npy stack [n, H, W]')
     ap.add_argument('--density', type=float, default=0.2, help='dtu: sampling and thinning distance')
+    ap.add_argument('--search', choices=('brute', 'grid'), default='brute',
+                    help='dtu: the two closing nearest-neighbour queries by brute force or through the grid')
     ap.add_argument('--scale-mat', default=None)
     ap.add_argument('--threshold', type=float, default=0.05)
     ap.add_argument('--down-sample', type=float, default=0.02, help='scannet: voxel size (0: none)')
