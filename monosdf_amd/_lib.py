@@ -250,6 +250,16 @@ _GRIDNN_SIGNATURES = {
                        C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P],
 }
 
+# The entry points of include/monosdf_meshcc.h (csrc/meshcc.hip): additive in the same way.
+_MESHCC_SIGNATURES = {
+    'msdf_mcc_edge_keys': [_P, C.c_int64, _P, _P],
+    'msdf_mcc_init': [_P, C.c_int64, _P],
+    'msdf_mcc_link_edges': [_P, _P, C.c_int64, C.c_int, _P, _P],
+    'msdf_mcc_link_vertices': [_P, C.c_int64, _P, _P],
+    'msdf_mcc_flatten': [_P, C.c_int64, _P],
+    'msdf_mcc_segment_sum': [_P, _P, C.c_int64, _P, _P],
+}
+
 _lib = None
 
 
@@ -263,7 +273,8 @@ def load():
             'monosdf_amd: %s not found -- build it with `python __graft_entry__.py` or '
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()):
+    for name, argtypes in (list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()) +
+                           list(_MESHCC_SIGNATURES.items())):
         fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int
