@@ -260,6 +260,13 @@ _MESHCC_SIGNATURES = {
     'msdf_mcc_segment_sum': [_P, _P, C.c_int64, _P, _P],
 }
 
+# The entry points of include/monosdf_obb.h (csrc/obb.hip): additive in the same way.
+_OBB_SIGNATURES = {
+    'msdf_obb_support_workspace_bytes': [C.c_int64, C.c_int64],
+    'msdf_obb_support': [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P],
+    'msdf_obb_candidates': [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P],
+}
+
 _lib = None
 
 
@@ -274,7 +281,7 @@ def load():
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in (list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()) +
-                           list(_MESHCC_SIGNATURES.items())):
+                           list(_MESHCC_SIGNATURES.items()) + list(_OBB_SIGNATURES.items())):
         fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int

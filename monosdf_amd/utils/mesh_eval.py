@@ -14,9 +14,11 @@
 
 Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by utils/mesh_args.py: every function
 that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_face_cross``.
-Out of scope: ICP alignment (``get_align_transformation``), the oriented-bounding-box crop of ``calc_3d_metric``
-(eval_recon.py:121-136), and an unbounded grid- or tree-accelerated search: the means of the ScanNet and Replica
-protocols need every distance, their brute-force searches take milliseconds, and brute force is the exact baseline
+The oriented-bounding-box crop that ``calc_3d_metric`` applies first (eval_recon.py:121-136) is in
+utils/mesh_bounds.py; ``evaluate_replica(..., crop=True)`` runs it.
+Out of scope: ICP alignment (``get_align_transformation``, dead code in the reference: ``align`` defaults to False),
+the coloured error clouds that ``calc_3d_metric`` writes, ``calc_2d_metric``, and an unbounded grid- or
+tree-accelerated search: the means of the ScanNet and Replica protocols need every distance, their brute-force searches take milliseconds, and brute force is the exact baseline
 that ``nearest_neighbors_within`` is checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to the predicted mesh
 before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol and its mask culling are in
 utils/mesh_dtu.py.
@@ -260,7 +262,7 @@ def evaluate_scannet(pred_vertices, gt_vertices, threshold=0.05, down_sample=0.0
     return {'Acc': acc, 'Comp': comp, 'Prec': prec, 'Recal': recal, 'F-score': _fscore(prec, recal)}
 
 
-def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_samples=False):
+def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_samples=False, crop=False):
     """The metrics of ``calc_3d_metric`` (replica_eval/eval_recon.py:138-177).  ``rec``, ``gt``: Mesh objects or
     (vertices [V,3], faces [F,3]) pairs (CUDA tensors, or numpy arrays, which are uploaded).  ``n_samples``
     area-weighted surface samples of each mesh (``seed`` fixes them), nearest neighbours both ways, then:
@@ -270,11 +272,16 @@ def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_sam
       'chamfer'   (accuracy + completion) / 2, cm
       'normal_acc' / 'normal_comp'  mean |cos| between the face normal of a rec / gt sample and the face normal of its
                   nearest neighbour in the other cloud, %;  'normal_avg' their mean.
-    The reference draws a second set of samples for the normals; here one set serves both.  Not done here: the ICP
-    alignment and the oriented-bounding-box crop that ``calc_3d_metric`` applies first (pass meshes already aligned
-    and cropped).  ``return_samples``: also a dict with 'rec_points', 'rec_faces', 'gt_points', 'gt_faces' (the samples
-    and the face each came from), 'rec_normals', 'gt_normals' (per sample)."""
+    The reference draws a second set of samples for the normals; here one set serves both.  ``crop``: True crops
+    ``rec`` to the oriented bounding box of ``gt`` scaled by 1.05 first, as ``calc_3d_metric`` always does
+    (eval_recon.py:121-136; utils/mesh_bounds.crop_to_oriented_bounds); False (the default) scores ``rec`` as it came.
+    Not done here: the ICP alignment (pass meshes already aligned).  ``return_samples``: also a dict with
+    'rec_points', 'rec_faces', 'gt_points', 'gt_faces' (the samples and the face each came from), 'rec_normals',
+    'gt_normals' (per sample)."""
     name = 'evaluate_replica'
+    if crop:
+        from .mesh_bounds import crop_to_oriented_bounds
+        rec = crop_to_oriented_bounds(rec, gt)
     rv, rf, _ = ma.mesh_tensors(name, rec, ma.device_of(*ma.mesh_parts(gt)))
     gv, gf, _ = ma.mesh_tensors(name, gt, rv.device)
     ma.same_device(name, rec=rv, gt=gv)
