@@ -267,6 +267,13 @@ _OBB_SIGNATURES = {
     'msdf_obb_candidates': [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P],
 }
 
+# The entry points of include/monosdf_highres.h (csrc/highres.hip): additive in the same way.
+_HIGHRES_SIGNATURES = {
+    'msdf_hrc_workspace_bytes': [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64],
+    'msdf_hrc_merge_depth': [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P],
+    'msdf_hrc_merge_normals': [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P],
+}
+
 _lib = None
 
 
@@ -281,7 +288,8 @@ def load():
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in (list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()) +
-                           list(_MESHCC_SIGNATURES.items()) + list(_OBB_SIGNATURES.items())):
+                           list(_MESHCC_SIGNATURES.items()) + list(_OBB_SIGNATURES.items()) +
+                           list(_HIGHRES_SIGNATURES.items())):
         fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int
