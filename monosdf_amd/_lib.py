@@ -274,6 +274,15 @@ _HIGHRES_SIGNATURES = {
     'msdf_hrc_merge_normals': [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P],
 }
 
+# The entry points of include/monosdf_icp.h (csrc/icp.hip): additive in the same way.
+_ICP_SIGNATURES = {
+    'msdf_icp_state_bytes': [C.c_int64],
+    'msdf_icp_workspace_bytes': [C.c_int64],
+    'msdf_icp_transform': [_P, C.c_int64, _P, _P, _P],
+    'msdf_icp_accumulate': [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P],
+    'msdf_icp_solve': [_P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P, _P],
+}
+
 _lib = None
 
 
@@ -289,7 +298,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in (list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()) +
                            list(_MESHCC_SIGNATURES.items()) + list(_OBB_SIGNATURES.items()) +
-                           list(_HIGHRES_SIGNATURES.items())):
+                           list(_HIGHRES_SIGNATURES.items()) + list(_ICP_SIGNATURES.items())):
         fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int

@@ -16,8 +16,9 @@ Everything runs on CUDA tensors; there is no CPU path.  Arguments are checked by
 that takes a mesh validates it once (``mesh_tensors``) and hands it on to the unchecked ``_face_cross``.
 The oriented-bounding-box crop that ``calc_3d_metric`` applies first (eval_recon.py:121-136) is in
 utils/mesh_bounds.py; ``evaluate_replica(..., crop=True)`` runs it.
-Out of scope: ICP alignment (``get_align_transformation``, dead code in the reference: ``align`` defaults to False),
-the coloured error clouds that ``calc_3d_metric`` writes, ``calc_2d_metric``, and an unbounded grid- or
+The ICP alignment (``get_align_transformation``, which ``calc_3d_metric(align=True)`` runs first) is in
+utils/mesh_align.py; ``evaluate_replica(..., align=True)`` runs it.
+Out of scope: the coloured error clouds that ``calc_3d_metric`` writes, ``calc_2d_metric``, and an unbounded grid- or
 tree-accelerated search: the means of the ScanNet and Replica protocols need every distance, their brute-force searches take milliseconds, and brute force is the exact baseline
 that ``nearest_neighbors_within`` is checked against.  View culling and TSDF re-fusion (``refuse``), which the reference applies to the predicted mesh
 before it calls these metrics, are in utils/mesh_refuse.py; the DTU protocol and its mask culling are in
@@ -73,6 +74,14 @@ def _positive(name, arg, value):
     return v
 
 
+def _search_distance(name, max_dist):
+    """``max_dist`` of a bounded search as a Python float: positive and finite, as a float32 too."""
+    md = _positive(name, 'max_dist', max_dist)
+    if md > float(np.finfo(np.float32).max):
+        raise ValueError('%s: max_dist must be finite as a float32, got %r' % (name, max_dist))
+    return md
+
+
 def grid_dims(lo, hi, h, max_cells):
     """The grid of ``nearest_neighbors_within`` over the box lo..hi (three Python floats each): the cell side, ``h``
     enlarged by steps of a quarter until the cell count fits ``max_cells``, and the cells per axis,
@@ -102,9 +111,7 @@ def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=No
     ma.check_tensor(name, 'reference', reference)
     ma.check_tensor(name, 'query', query)
     dev = ma.same_device(name, reference=reference, query=query)
-    md = _positive(name, 'max_dist', max_dist)
-    if md > float(np.finfo(np.float32).max):
-        raise ValueError('%s: max_dist must be finite as a float32, got %r' % (name, max_dist))
+    md = _search_distance(name, max_dist)
     h = md / GRID_CELL_FRACTION if cell is None else _positive(name, 'cell', cell)
     cap = GRID_MAX_CELLS if max_cells is None else _positive(name, 'max_cells', max_cells)
     R, Q = reference.shape[0], query.shape[0]
@@ -116,10 +123,17 @@ def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=No
         raise ValueError('%s: non-finite coordinates' % name)
     if Q == 0:
         return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+    with torch.cuda.device(dev):
+        return _grid_query(qry, _grid_build(ref, _grid_over(lo_h, hi_h, h, cap)), md)
+
+
+def _grid_over(lo_h, hi_h, h, cap):
+    """The ``grid`` of ``_grid_build`` over the box lo_h..hi_h (fp64 host tensors [3]) for the cell side ``h`` and the
+    cap ``cap`` of the cell count: what ``nearest_neighbors_within`` searches through (utils/mesh_align.py builds the
+    same grid once per alignment)."""
     lo = lo_h.tolist()
     h, dims = grid_dims(lo, hi_h.tolist(), h, max(1, int(min(cap, _GRID_CELLS_LIMIT))))
-    with torch.cuda.device(dev):
-        return _grid_query(qry, _grid_build(ref, (*lo, h, *dims)), md)
+    return (*lo, h, *dims)
 
 
 def _grid_build(ref, grid):
@@ -138,6 +152,12 @@ def _grid_build(ref, grid):
 def _grid_query(qry, built, max_dist):
     """The answer of ``nearest_neighbors_within`` for the queries (checked, contiguous, at least one, on the current
     device) against what ``_grid_build`` returned."""
+    dist, idx = _grid_query_int32(qry, built, max_dist)
+    return dist, idx.long()
+
+
+def _grid_query_int32(qry, built, max_dist):
+    """``_grid_query`` with the indices as msdf_gnn_query wrote them (int32), which the ICP kernels read."""
     grid, n_ref, records, starts = built
     Q, dev = qry.shape[0], qry.device
     cells = torch.empty(Q, dtype=torch.int32, device=dev)
@@ -146,7 +166,7 @@ def _grid_query(qry, built, max_dist):
     dist = torch.empty(Q, dtype=torch.float32, device=dev)
     idx = torch.empty(Q, dtype=torch.int32, device=dev)
     ma.call('msdf_gnn_query', qry, order, Q, records, n_ref, starts, *grid, max_dist, dist, idx)
-    return dist, idx.long()
+    return dist, idx
 
 
 _VOXEL_AXIS_MAX = 2 ** 21            # cells per axis the 63-bit voxel key holds
@@ -262,7 +282,7 @@ def evaluate_scannet(pred_vertices, gt_vertices, threshold=0.05, down_sample=0.0
     return {'Acc': acc, 'Comp': comp, 'Prec': prec, 'Recal': recal, 'F-score': _fscore(prec, recal)}
 
 
-def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_samples=False, crop=False):
+def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_samples=False, crop=False, align=False):
     """The metrics of ``calc_3d_metric`` (replica_eval/eval_recon.py:138-177).  ``rec``, ``gt``: Mesh objects or
     (vertices [V,3], faces [F,3]) pairs (CUDA tensors, or numpy arrays, which are uploaded).  ``n_samples``
     area-weighted surface samples of each mesh (``seed`` fixes them), nearest neighbours both ways, then:
@@ -275,10 +295,15 @@ def evaluate_replica(rec, gt, n_samples=200000, dist_th=0.05, seed=0, return_sam
     The reference draws a second set of samples for the normals; here one set serves both.  ``crop``: True crops
     ``rec`` to the oriented bounding box of ``gt`` scaled by 1.05 first, as ``calc_3d_metric`` always does
     (eval_recon.py:121-136; utils/mesh_bounds.crop_to_oriented_bounds); False (the default) scores ``rec`` as it came.
-    Not done here: the ICP alignment (pass meshes already aligned).  ``return_samples``: also a dict with
+    ``align``: True first moves ``rec`` onto ``gt`` by point-to-point ICP on the vertices, before the crop, the order
+    of ``calc_3d_metric(align=True)`` (eval_recon.py:51-65, 113-117; utils/mesh_align.align_mesh, whose parity with
+    open3d's ICP is unverified); False (the default) takes the meshes as aligned.  ``return_samples``: also a dict with
     'rec_points', 'rec_faces', 'gt_points', 'gt_faces' (the samples and the face each came from), 'rec_normals',
     'gt_normals' (per sample)."""
     name = 'evaluate_replica'
+    if align:
+        from .mesh_align import align_mesh
+        rec = align_mesh(rec, gt)[0]
     if crop:
         from .mesh_bounds import crop_to_oriented_bounds
         rec = crop_to_oriented_bounds(rec, gt)

@@ -1,6 +1,6 @@
 """Metrics of a reconstructed mesh against a ground-truth mesh, on the GPU, as one JSON line.
 
-    python scripts/eval_mesh.py PRED.ply GT.ply --protocol scannet|replica [--scale-mat cameras.npz] [--crop]
+    python scripts/eval_mesh.py PRED.ply GT.ply --protocol scannet|replica [--scale-mat cameras.npz] [--crop] [--align]
     python scripts/eval_mesh.py PRED.ply --protocol dtu --dtu-dir DTU --scan 24 [--cameras cameras.npz --masks DIR|NPY]
                                          [--search brute|grid]
 
@@ -13,9 +13,10 @@ ObsMask/ and Points/stl/ folders.  Prints d2s, s2d and their mean in millimetres
 distance queries through the grid-bounded search (nearest_neighbors_within): the same numbers, sooner.
 --scale-mat: a cameras.npz whose `scale_mat_0` takes the predicted mesh from the normalised training frame to the
 world frame (evaluation/eval.py applies it before it writes the mesh; pass it when PRED.ply was written without).
-The meshes must be aligned already: ICP is not done here.  --crop (replica) first crops PRED to the oriented bounding
-box of GT scaled by 1.05, as calc_3d_metric() always does (monosdf_amd/utils/mesh_bounds.py); without it PRED is scored
-as it came.
+--align (replica) first moves PRED onto GT by point-to-point ICP on the vertices, as calc_3d_metric(align=True) does
+(monosdf_amd/utils/mesh_align.py; parity with open3d's ICP is unverified); without it the meshes must be aligned
+already.  --crop (replica) then crops PRED to the oriented bounding box of GT scaled by 1.05, as calc_3d_metric() always
+does (monosdf_amd/utils/mesh_bounds.py); without it PRED is scored as it came.
 The reference scores the re-fused (ScanNet) or frustum-culled (Replica) mesh: make PRED.ply with scripts/refuse_mesh.py.
 """
 import argparse
@@ -66,10 +67,14 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--crop', action='store_true',
                     help='replica: crop PRED to the oriented bounding box of GT scaled by 1.05 first')
+    ap.add_argument('--align', action='store_true',
+                    help='replica: move PRED onto GT by point-to-point ICP on the vertices first')
     args = ap.parse_args()
     from monosdf_amd.utils import mesh_eval
     if args.crop and args.protocol != 'replica':
         ap.error('--crop belongs to --protocol replica')
+    if args.align and args.protocol != 'replica':
+        ap.error('--align belongs to --protocol replica')
     if args.protocol == 'dtu':
         print(json.dumps(evaluate_dtu(ap, args)))
         return
@@ -82,7 +87,7 @@ def main():
         out = mesh_eval.evaluate_scannet(pred, gt, threshold=args.threshold, down_sample=args.down_sample)
     else:
         out = mesh_eval.evaluate_replica(pred, gt, n_samples=args.n_samples, dist_th=args.threshold, seed=args.seed,
-                                           crop=args.crop)
+                                           crop=args.crop, align=args.align)
     print(json.dumps(out))
 
 
