@@ -1,4 +1,4 @@
-"""ctypes binding of libmonosdf_hip.so (C ABI declared in include/monosdf_hip.h).
+"""ctypes binding of libmonosdf_hip.so (C ABI declared in include/monosdf_hip.h and the additive headers beside it).
 
 The product path has no CPU or eager-PyTorch fallback: if the shared library is
 missing or a kernel launch fails, this module raises.
@@ -153,8 +153,14 @@ class SamplerArgs(Struct):
 
 _ERR = {1: 'invalid argument', 2: 'kernel launch failed', 3: 'unsupported configuration'}
 
-# name -> argtypes (restype is always int)
-_SIGNATURES = {
+ABI_VERSION = 8
+VERSIONED_HEADER = 'monosdf_hip.h'
+
+# The whole C ABI: header under include/ -> {entry: argtypes}; the return type is int, int64_t for a name that ends in
+# _bytes.  The first header is the versioned surface (ABI_VERSION, exported_symbols()); the others are additive, one
+# per feature, and leave that version alone.  load() binds what is here and nothing else, so an entry point of a new
+# header is one more key (tests/test_abi_cpu.py holds every header under include/ against its key).
+_ABI = {VERSIONED_HEADER: {
     'msdf_abi_version': [],
     'msdf_hash_encode_forward': [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.c_float, C.c_uint32, C.c_int, _P, _P],
@@ -235,55 +241,52 @@ _SIGNATURES = {
     'msdf_dtu_thin_prepare': [_P, _P, _P, _P, C.c_int64, _P, _P],
     'msdf_dtu_thin_round': [_P, C.c_int64, C.c_double, _P, _P],
     'msdf_dtu_thin_finish': [_P, _P, C.c_int64, _P, _P],
-}
-
-ABI_VERSION = 8
-
-# The entry points of include/monosdf_gridnn.h (csrc/gridnn.hip): additive, outside the versioned table above and its
-# header; load() binds both tables by the same rule.
-_GRIDNN_SIGNATURES = {
+}, 'monosdf_gridnn.h': {                                   # csrc/gridnn.hip
     'msdf_gnn_workspace_bytes': [C.c_int64],
     'msdf_gnn_cells': [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P,
                        _P],
     'msdf_gnn_records': [_P, _P, C.c_int64, _P, _P],
     'msdf_gnn_query': [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                        C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P],
-}
-
-# The entry points of include/monosdf_meshcc.h (csrc/meshcc.hip): additive in the same way.
-_MESHCC_SIGNATURES = {
+}, 'monosdf_meshcc.h': {                                   # csrc/meshcc.hip
     'msdf_mcc_edge_keys': [_P, C.c_int64, _P, _P],
     'msdf_mcc_init': [_P, C.c_int64, _P],
     'msdf_mcc_link_edges': [_P, _P, C.c_int64, C.c_int, _P, _P],
     'msdf_mcc_link_vertices': [_P, C.c_int64, _P, _P],
     'msdf_mcc_flatten': [_P, C.c_int64, _P],
     'msdf_mcc_segment_sum': [_P, _P, C.c_int64, _P, _P],
-}
-
-# The entry points of include/monosdf_obb.h (csrc/obb.hip): additive in the same way.
-_OBB_SIGNATURES = {
+}, 'monosdf_obb.h': {                                      # csrc/obb.hip
     'msdf_obb_support_workspace_bytes': [C.c_int64, C.c_int64],
     'msdf_obb_support': [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P],
     'msdf_obb_candidates': [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P],
-}
-
-# The entry points of include/monosdf_highres.h (csrc/highres.hip): additive in the same way.
-_HIGHRES_SIGNATURES = {
+}, 'monosdf_highres.h': {                                  # csrc/highres.hip
     'msdf_hrc_workspace_bytes': [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64],
     'msdf_hrc_merge_depth': [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P],
     'msdf_hrc_merge_normals': [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P],
-}
-
-# The entry points of include/monosdf_icp.h (csrc/icp.hip): additive in the same way.
-_ICP_SIGNATURES = {
+}, 'monosdf_icp.h': {                                      # csrc/icp.hip
     'msdf_icp_state_bytes': [C.c_int64],
     'msdf_icp_workspace_bytes': [C.c_int64],
     'msdf_icp_transform': [_P, C.c_int64, _P, _P, _P],
     'msdf_icp_accumulate': [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P],
     'msdf_icp_solve': [_P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P, _P],
-}
+}}
+
+_ENTRIES = [name for table in _ABI.values() for name in table]
+if len(_ENTRIES) != len(set(_ENTRIES)):
+    raise ImportError('monosdf_amd: bound under two headers: %s'
+                      % sorted(n for n in set(_ENTRIES) if _ENTRIES.count(n) > 1))
 
 _lib = None
+
+
+def headers():
+    """The header files under include/ that declare the ABI, the versioned one first."""
+    return list(_ABI)
+
+
+def signatures(header):
+    """{entry: argtypes} of one header of ``headers()``."""
+    return _ABI[header]
 
 
 def load():
@@ -296,12 +299,11 @@ def load():
             'monosdf_amd: %s not found -- build it with `python __graft_entry__.py` or '
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in (list(_SIGNATURES.items()) + list(_GRIDNN_SIGNATURES.items()) +
-                           list(_MESHCC_SIGNATURES.items()) + list(_OBB_SIGNATURES.items()) +
-                           list(_HIGHRES_SIGNATURES.items()) + list(_ICP_SIGNATURES.items())):
-        fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
-        fn.argtypes = argtypes
-        fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int
+    for table in _ABI.values():
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
+            fn.argtypes = argtypes
+            fn.restype = C.c_int64 if name.endswith('_bytes') else C.c_int
     if lib.msdf_abi_version() != ABI_VERSION:
         raise RuntimeError('monosdf_amd: ABI version mismatch, rebuild the library')
     _lib = lib
@@ -309,7 +311,8 @@ def load():
 
 
 def exported_symbols():
-    return sorted(_SIGNATURES)
+    """The sorted entry points of the versioned header."""
+    return sorted(_ABI[VERSIONED_HEADER])
 
 
 # bench.py sets this to a dict to collect (start, end) HIP events per entry point; they are recorded on

@@ -12,9 +12,9 @@ Everything runs on CUDA tensors (numpy arrays are uploaded); there is no CPU pat
 current stream -- transform, the target grid's cell kernel, a sort, the grid query, the 17 sums, the solve -- and the
 host reads nothing back inside it: the transform, the iteration count, the convergence test and the log live in one
 small device struct, every ICP kernel returns at once when its ``done`` flag is set, and the host looks at the flag
-once every ``check_every`` iterations.  The target's grid is built once (``mesh_eval``'s, the one
-``nearest_neighbors_within`` searches through).  No atomics: the same inputs give bitwise the same result every call
-and for every ``check_every``.
+once every ``check_every`` iterations.  The target's grid is one ``PointGrid`` (utils/point_grid.py, the object
+``nearest_neighbors_within`` searches through), built once per alignment and queried every iteration.  No atomics: the
+same inputs give bitwise the same result every call and for every ``check_every``.
 
 Two deliberate differences from open3d: it composes ``update @ T`` on a cloud that it transforms in place, here T is
 solved from the original points every iteration (the same optimum in exact arithmetic, no drift); it holds points in
@@ -26,7 +26,7 @@ import torch
 
 from .. import _lib
 from . import mesh_args as ma
-from . import mesh_eval as me
+from .point_grid import GRID_CELL_FRACTION, PointGrid
 
 _T_DOUBLES, _FLAG_WORD = 18, 37      # the state: T[16], prev_fitness, prev_rmse, then int32 iteration, done, then the log
 
@@ -81,7 +81,7 @@ def _run(name, src, tgt, md, T, max_iteration, relative_fitness, relative_rmse, 
     N, M = src.shape[0], tgt.shape[0]
     pivots, t_lo, t_hi = _pivots(name, src, tgt)
     with torch.cuda.device(dev):
-        built = me._grid_build(tgt, me._grid_over(t_lo, t_hi, md / me.GRID_CELL_FRACTION, me.GRID_MAX_CELLS))
+        grid = PointGrid(tgt, t_lo, t_hi, md / GRID_CELL_FRACTION)           # once per alignment
         state = _new_state(T, max_iteration, dev)
         flags = state.view(torch.int32)
         ws = ma.workspace(name, 'msdf_icp_workspace_bytes', N, device=dev)
@@ -89,7 +89,7 @@ def _run(name, src, tgt, md, T, max_iteration, relative_fitness, relative_rmse, 
         idx = None
         for k in range(max_iteration + 1):
             ma.call('msdf_icp_transform', src, N, state, y)
-            idx = me._grid_query_int32(y, built, md)[1]
+            idx = grid.query(y, md, int32=True)[1]
             ma.call('msdf_icp_accumulate', src, y, tgt, idx, N, M, pivots, state, ws)
             ma.call('msdf_icp_solve', ws, N, pivots, max_iteration, relative_fitness, relative_rmse, state)
             if (k + 1) % check_every == 0 and k < max_iteration and int(flags[_FLAG_WORD]):
@@ -119,7 +119,7 @@ def icp(source, target, max_dist=0.1, init=None, max_iteration=30, relative_fitn
     src = _cloud(name, 'source', source, dev)
     tgt = _cloud(name, 'target', target, src.device)
     ma.same_device(name, source=src, target=tgt)
-    md = me._search_distance(name, max_dist)
+    md = ma.search_distance(name, max_dist)
     T = _matrix(name, 'init', init)
     max_iteration, check_every = int(max_iteration), int(check_every)
     if max_iteration < 0:
@@ -140,7 +140,7 @@ def evaluate_registration(source, target, max_dist, transformation=None):
     src = _cloud(name, 'source', source, dev)
     tgt = _cloud(name, 'target', target, src.device)
     ma.same_device(name, source=src, target=tgt)
-    md = me._search_distance(name, max_dist)
+    md = ma.search_distance(name, max_dist)
     state, _, idx = _run(name, src, tgt, md, _matrix(name, 'transformation', transformation), 0, 0.0, 0.0, 1)
     log = _read_state(state)[2]
     return float(log[0, 0]), float(log[0, 1]), idx.long()

@@ -1,5 +1,6 @@
-"""Argument handling of the mesh tools (utils/mesh.py, mesh_eval.py, mesh_refuse.py, mesh_dtu.py): each rule their
-entry points apply before a kernel sees a pointer, stated once.
+"""Argument handling of the mesh tools (utils/mesh.py, mesh_eval.py, mesh_refuse.py, mesh_dtu.py, mesh_clean.py,
+mesh_bounds.py, mesh_align.py, point_grid.py): each rule their entry points apply before a kernel sees a pointer, and
+the one way a culled mesh goes back to the caller, stated once.
 
 * ``check_tensor``, ``same_device``: the CUDA tensor an entry point accepts (there is no CPU path).
 * ``mesh_tensors``: a mesh object or a (vertices, faces) pair -> float32 / int32 device tensors, its contents checked
@@ -8,6 +9,8 @@ entry points apply before a kernel sees a pointer, stated once.
   and ``.vertex_normals`` (utils/mesh.py's Mesh, a trimesh.Trimesh).
 * ``workspace``, ``call``: the scratch buffer an ABI entry asks for, and the call itself.
 * ``compact_faces``, ``finite_bounds``: dropping vertices with their faces; the bounding box of a cloud.
+* ``positive_number``, ``search_distance``: a cell side, a radius, a density, a search bound.
+* ``host_array``, ``kept_mesh``: the kept vertices, their normals and the re-indexed faces as a Mesh on the host.
 
 Every error begins with the public function's name, which the caller passes as ``name``.
 """
@@ -133,6 +136,40 @@ def compact_faces(keep, faces, all_kept=False):
     if not all_kept:
         f = f[keep[f].all(dim=1)]
     return (torch.cumsum(keep, 0) - 1)[f].reshape(-1, 3)
+
+
+def host_array(a):
+    """A tensor (any device) or a host array as a numpy array."""
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def kept_mesh(vertices, normals, keep, faces):
+    """The Mesh of the rows ``keep`` (bool [V], a tensor on any device) of ``vertices`` and, unless None, ``normals``
+    (each a tensor or a host array), with ``faces`` as they are: already re-indexed to those rows (``compact_faces``).
+    Mesh converts to fp64 / int64 itself."""
+    from .mesh import Mesh                                     # at call time: utils/mesh.py imports this module
+    keep_h = host_array(keep)
+    return Mesh(host_array(vertices)[keep_h], host_array(faces),
+                None if normals is None else host_array(normals)[keep_h])
+
+
+def positive_number(name, arg, value):
+    """``value`` as a Python float; ValueError unless it is a number, positive and finite."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: %s must be a number, got %r' % (name, arg, value))
+    if not (v > 0.0 and np.isfinite(v)):
+        raise ValueError('%s: %s must be positive and finite, got %r' % (name, arg, value))
+    return v
+
+
+def search_distance(name, max_dist):
+    """``max_dist`` of a bounded search as a Python float: positive and finite, as a float32 too."""
+    md = positive_number(name, 'max_dist', max_dist)
+    if md > float(np.finfo(np.float32).max):
+        raise ValueError('%s: max_dist must be finite as a float32, got %r' % (name, max_dist))
+    return md
 
 
 def finite_bounds(name, points):

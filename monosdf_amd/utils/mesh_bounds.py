@@ -27,7 +27,6 @@ import numpy as np
 import torch
 
 from . import mesh_args as ma
-from .mesh import Mesh
 
 TOL_SCALE = 1e-12                     # tol = this times the largest absolute coordinate
 MAX_ROUNDS = 100                      # hull rounds before convex_hull gives up (measured: 4 ... 8)
@@ -454,10 +453,6 @@ def oriented_bounds(mesh_or_points):
 
 # ---------------------------------------------------------------- the crop
 
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
 def crop_to_oriented_bounds(rec, gt, margin=1.05):
     """Lines 122-136 of ``calc_3d_metric`` (replica_eval/eval_recon.py) -> Mesh: ``rec`` without the vertices outside
     the oriented bounding box of ``gt`` scaled by ``margin``, and without the faces that touch one.  ``rec``, ``gt``:
@@ -477,9 +472,4 @@ def crop_to_oriented_bounds(rec, gt, margin=1.05):
     r = (rot @ rv.double().T + shift).T
     lo, hi = g.min(dim=0).values * float(margin), g.max(dim=0).values * float(margin)
     keep = ((r - lo[None]) > 0).all(dim=1) & ((r - hi[None]) < 0).all(dim=1)
-    faces = ma.compact_faces(keep, rf).cpu().numpy()
-    keep_h = keep.cpu().numpy()
-    vertices = _host(ma.mesh_parts(rec)[0])[keep_h]
-    if normals is None:
-        return Mesh(vertices, faces)
-    return Mesh(vertices, faces, _host(normals)[keep_h])
+    return ma.kept_mesh(ma.mesh_parts(rec)[0], normals, keep, ma.compact_faces(keep, rf))

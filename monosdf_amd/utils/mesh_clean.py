@@ -136,15 +136,9 @@ def _select(name, mesh, v, f, normals, keep_faces):
     kept = f[keep_faces]
     keep = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
     keep[kept.long().reshape(-1)] = True
-    faces = ma.compact_faces(keep, kept, all_kept=True).cpu().numpy()
-    if normals is None:                                # a (vertices, faces) pair
-        return Mesh(v[keep].double().cpu().numpy(), faces)
-    keep_h = keep.cpu().numpy()
-    return Mesh(_host(ma.mesh_parts(mesh)[0])[keep_h], faces, _host(normals)[keep_h])
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    faces = ma.compact_faces(keep, kept, all_kept=True)
+    # a (vertices, faces) pair comes back as what was searched, a mesh object with its own vertices and normals
+    return ma.kept_mesh(v if normals is None else ma.mesh_parts(mesh)[0], normals, keep, faces)
 
 
 def largest_component(mesh, connectivity='edge', by='area'):
@@ -242,14 +236,10 @@ def merge_vertices(mesh, digits=8):
         keys = ma.upload(host_keys, dev)
     V = v.shape[0]
     if V == 0:
-        return Mesh(np.zeros((0, 3)), _host(f))
+        return Mesh(np.zeros((0, 3)), ma.host_array(f))
     distinct, inverse = torch.unique(keys, dim=0, return_inverse=True)
     index = torch.arange(V, device=dev)
     first = torch.full((distinct.shape[0],), V, dtype=torch.int64, device=dev)
     first = first.scatter_reduce(0, inverse, index, 'amin')[inverse]           # per vertex: the one it merges into
     keep = first == index
-    faces = (torch.cumsum(keep, 0) - 1)[first[f.long()]].reshape(-1, 3).cpu().numpy()
-    keep_h = keep.cpu().numpy()
-    if normals is None:
-        return Mesh(_host(hv)[keep_h], faces)
-    return Mesh(_host(hv)[keep_h], faces, _host(normals)[keep_h])
+    return ma.kept_mesh(hv, normals, keep, (torch.cumsum(keep, 0) - 1)[first[f.long()]].reshape(-1, 3))

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import mesh_args as ma
-from .mesh import Mesh, read_ply
+from .mesh import read_ply
 from .mesh_eval import nearest_neighbors, nearest_neighbors_within
 
 MAX_RADIUS = 32                      # pixels: the dilation kernel reads a word and its two neighbours
@@ -135,11 +135,8 @@ def cull_to_masks(mesh, projections, masks, radius=12):
     if isinstance(masks, np.ndarray):
         masks = ma.upload((masks != 0).view(np.uint8), v.device)
     keep = mask_vertices(v, projections, dilate_masks(masks, radius))
-    faces = ma.compact_faces(keep, f).cpu().numpy()
-    if nrm is None:                                    # a (vertices, faces) pair
-        return Mesh(v[keep].double().cpu().numpy(), faces)
-    keep_h = keep.cpu().numpy()
-    return Mesh(mesh.vertices[keep_h], faces, nrm[keep_h])
+    # a (vertices, faces) pair comes back as what was culled, a mesh object with its own vertices and normals
+    return ma.kept_mesh(v if nrm is None else mesh.vertices, nrm, keep, ma.compact_faces(keep, f))
 
 
 def sample_lattice(vertices, faces, density=0.2):
@@ -150,15 +147,8 @@ def sample_lattice(vertices, faces, density=0.2):
     a = (i + 0.5) / max(n1, 1e-7) for i = 0..n1 and b = (j + 0.5) / max(n2, 1e-7) for j = 0..n2, kept iff a + b < 1;
     point = (v1 a + v2 b) + p0, rounded once to fp32.  Output order: face ascending, then i, then j.  The vertices
     themselves are not included: the caller concatenates them, as the reference does.  ValueError at 2^31 points."""
-    dens = _density('sample_lattice', density)
+    dens = ma.positive_number('sample_lattice', 'density', density)
     return _lattice(*ma.mesh_tensors('sample_lattice', (vertices, faces))[:2], dens)
-
-
-def _density(name, density):
-    dens = float(density)
-    if not (dens > 0.0 and np.isfinite(dens)):
-        raise ValueError('%s: density must be positive and finite, got %r' % (name, density))
-    return dens
 
 
 def _lattice(v, f, dens):
@@ -196,12 +186,7 @@ def radius_thin(points, radius, order=None, return_rounds=False):
     than the radius (27 cells per point); the host reads the undecided count once per round.
     ``return_rounds``: also the number of rounds that ran."""
     name = 'radius_thin'
-    try:
-        r = float(radius)
-    except (TypeError, ValueError):
-        raise ValueError('%s: radius must be a number, got %r' % (name, radius))
-    if not (r > 0.0 and np.isfinite(r)):
-        raise ValueError('%s: radius must be positive and finite, got %r' % (name, radius))
+    r = ma.positive_number(name, 'radius', radius)
     if order is not None:
         if not isinstance(order, torch.Tensor) or order.dtype != torch.int64 or order.dim() != 1:
             raise ValueError('%s: order must be a 1-D int64 tensor' % name)
@@ -279,7 +264,7 @@ def evaluate_dtu(mesh_or_points, stl_points, obs_mask, bb, res, plane, density=0
     dev = ma.device_of(stl_points, obs_mask)
     if isinstance(mesh_or_points, (tuple, list)) or hasattr(mesh_or_points, 'faces'):
         v, f, _ = ma.mesh_tensors(name, mesh_or_points, dev)
-        cloud = torch.cat([v, _lattice(v, f, _density(name, density))])
+        cloud = torch.cat([v, _lattice(v, f, ma.positive_number(name, 'density', density))])
     else:
         cloud = ma.cloud_tensor(name, 'points', mesh_or_points, dev)
     dev = cloud.device

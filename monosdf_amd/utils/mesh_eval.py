@@ -4,8 +4,9 @@
   sklearn's ``KDTree(...).query`` (scannet_eval/evaluate.py:16-26) and scipy's ``cKDTree(...).query``
   (replica_eval/eval_recon.py:25-43, 96-106).
 * ``nearest_neighbors_within``: the same answer, bit for bit, for the queries that have a reference point within
-  ``max_dist``, through a uniform grid (csrc/gridnn.hip, ABI msdf_gnn_* of include/monosdf_gridnn.h): the search of the
-  DTU protocol's two closing queries, which use only the distances below ``max_dist``.
+  ``max_dist``, through a uniform grid (utils/point_grid.py's ``PointGrid``, built and queried once per call;
+  csrc/gridnn.hip): the search of the DTU protocol's two closing queries, which use only the distances below
+  ``max_dist``.  ``grid_dims`` and the two ``GRID_*`` defaults of that module are importable from here too.
 * ``voxel_down_sample``: the rule of open3d's ``PointCloud.voxel_down_sample`` (evaluate.py:36-38; ABI msdf_voxel_*).
 * ``sample_surface``, ``face_normals``: trimesh.sample.sample_surface and Trimesh.face_normals (eval_recon.py:138-158).
 * ``evaluate_scannet``: ``evaluate`` (evaluate.py:29-56).  ``evaluate_replica``: the metrics of ``calc_3d_metric``
@@ -29,6 +30,7 @@ import torch
 
 from . import mesh_args as ma
 from .mesh import read_ply                                   # noqa: F401 (public here too)
+from .point_grid import GRID_CELL_FRACTION, GRID_MAX_CELLS, PointGrid, grid_dims    # noqa: F401 (public here too)
 
 
 def nearest_neighbors(reference, query, n_splits=0):
@@ -59,40 +61,6 @@ def nearest_neighbors(reference, query, n_splits=0):
     return dist, idx.long()
 
 
-GRID_CELL_FRACTION = 16              # default cell side: max_dist over this (the best of the sweep of DESIGN 4.12)
-GRID_MAX_CELLS = 2 ** 25             # default cap of the cell count: a start table of 128 MiB (unmeasured)
-_GRID_CELLS_LIMIT = 2 ** 31 - 2      # the start table is indexed in int32
-
-
-def _positive(name, arg, value):
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError('%s: %s must be a number, got %r' % (name, arg, value))
-    if not (v > 0.0 and np.isfinite(v)):
-        raise ValueError('%s: %s must be positive and finite, got %r' % (name, arg, value))
-    return v
-
-
-def _search_distance(name, max_dist):
-    """``max_dist`` of a bounded search as a Python float: positive and finite, as a float32 too."""
-    md = _positive(name, 'max_dist', max_dist)
-    if md > float(np.finfo(np.float32).max):
-        raise ValueError('%s: max_dist must be finite as a float32, got %r' % (name, max_dist))
-    return md
-
-
-def grid_dims(lo, hi, h, max_cells):
-    """The grid of ``nearest_neighbors_within`` over the box lo..hi (three Python floats each): the cell side, ``h``
-    enlarged by steps of a quarter until the cell count fits ``max_cells``, and the cells per axis,
-    floor((hi - lo) / h) + 1 in fp64, the expression that gives a point its cell.  -> (h, (nx, ny, nz))"""
-    while True:
-        n = [np.floor((b - a) / h) + 1.0 for a, b in zip(lo, hi)]
-        if n[0] * n[1] * n[2] <= max_cells:
-            return h, tuple(int(c) for c in n)
-        h *= 1.25
-
-
 def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=None):
     """``nearest_neighbors(reference, query)`` for the queries that have a reference point within ``max_dist``:
     ``(dist [Q] float32, idx [Q] int64)``.  With (d, i) what ``nearest_neighbors`` returns for a query: bitwise (d, i)
@@ -111,9 +79,9 @@ def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=No
     ma.check_tensor(name, 'reference', reference)
     ma.check_tensor(name, 'query', query)
     dev = ma.same_device(name, reference=reference, query=query)
-    md = _search_distance(name, max_dist)
-    h = md / GRID_CELL_FRACTION if cell is None else _positive(name, 'cell', cell)
-    cap = GRID_MAX_CELLS if max_cells is None else _positive(name, 'max_cells', max_cells)
+    md = ma.search_distance(name, max_dist)
+    h = md / GRID_CELL_FRACTION if cell is None else ma.positive_number(name, 'cell', cell)
+    cap = GRID_MAX_CELLS if max_cells is None else ma.positive_number(name, 'max_cells', max_cells)
     R, Q = reference.shape[0], query.shape[0]
     if R == 0:
         raise ValueError('%s: the reference cloud is empty' % name)
@@ -124,49 +92,7 @@ def nearest_neighbors_within(reference, query, max_dist, cell=None, max_cells=No
     if Q == 0:
         return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
     with torch.cuda.device(dev):
-        return _grid_query(qry, _grid_build(ref, _grid_over(lo_h, hi_h, h, cap)), md)
-
-
-def _grid_over(lo_h, hi_h, h, cap):
-    """The ``grid`` of ``_grid_build`` over the box lo_h..hi_h (fp64 host tensors [3]) for the cell side ``h`` and the
-    cap ``cap`` of the cell count: what ``nearest_neighbors_within`` searches through (utils/mesh_align.py builds the
-    same grid once per alignment)."""
-    lo = lo_h.tolist()
-    h, dims = grid_dims(lo, hi_h.tolist(), h, max(1, int(min(cap, _GRID_CELLS_LIMIT))))
-    return (*lo, h, *dims)
-
-
-def _grid_build(ref, grid):
-    """The reference cloud (checked, contiguous, on the current device) in the cells of ``grid`` = (lo_x, lo_y, lo_z,
-    h, nx, ny, nz): -> (grid, R, records, starts), the arguments of msdf_gnn_query."""
-    R, dev = ref.shape[0], ref.device
-    cells = torch.empty(R, dtype=torch.int32, device=dev)
-    ma.call('msdf_gnn_cells', ref, R, *grid, cells)
-    sorted_cells, order = torch.sort(cells, stable=True)
-    records = ma.workspace('nearest_neighbors_within', 'msdf_gnn_workspace_bytes', R, device=dev)
-    ma.call('msdf_gnn_records', ref, order, R, records)
-    every_cell = torch.arange(grid[4] * grid[5] * grid[6] + 1, dtype=torch.int32, device=dev)
-    return grid, R, records, torch.searchsorted(sorted_cells, every_cell, out_int32=True)
-
-
-def _grid_query(qry, built, max_dist):
-    """The answer of ``nearest_neighbors_within`` for the queries (checked, contiguous, at least one, on the current
-    device) against what ``_grid_build`` returned."""
-    dist, idx = _grid_query_int32(qry, built, max_dist)
-    return dist, idx.long()
-
-
-def _grid_query_int32(qry, built, max_dist):
-    """``_grid_query`` with the indices as msdf_gnn_query wrote them (int32), which the ICP kernels read."""
-    grid, n_ref, records, starts = built
-    Q, dev = qry.shape[0], qry.device
-    cells = torch.empty(Q, dtype=torch.int32, device=dev)
-    ma.call('msdf_gnn_cells', qry, Q, *grid, cells)
-    order = torch.sort(cells, stable=True)[1]
-    dist = torch.empty(Q, dtype=torch.float32, device=dev)
-    idx = torch.empty(Q, dtype=torch.int32, device=dev)
-    ma.call('msdf_gnn_query', qry, order, Q, records, n_ref, starts, *grid, max_dist, dist, idx)
-    return dist, idx
+        return PointGrid(ref, lo_h, hi_h, h, cap).query(qry, md)
 
 
 _VOXEL_AXIS_MAX = 2 ** 21            # cells per axis the 63-bit voxel key holds

@@ -74,14 +74,13 @@ def grid_stages(reference, query, max_dist, cell, repeats):
     """nearest_neighbors_within(reference, query, max_dist, cell): the whole call, and its two halves apart."""
     from monosdf_amd.utils import mesh_args as ma
     from monosdf_amd.utils import mesh_eval as me
+    from monosdf_amd.utils.point_grid import PointGrid
     whole, result = timed(lambda: me.nearest_neighbors_within(reference, query, max_dist, cell=cell), repeats)
     _, lo, hi = ma.finite_bounds('bench_dtu_eval', reference)
-    h, dims = me.grid_dims(lo.tolist(), hi.tolist(), cell, me.GRID_MAX_CELLS)
-    grid = (*lo.tolist(), h, *dims)
-    build, built = timed(lambda: me._grid_build(reference, grid), repeats)
-    search, _ = timed(lambda: me._grid_query(query, built, max_dist), repeats)
-    return {'cell_asked': cell, 'cell': round(h, 6), 'cells': list(dims), 'ms': whole['ms'], 'ms_all': whole['ms_all'],
-            'build_ms': build['ms'], 'query_ms': search['ms']}, result
+    build, grid = timed(lambda: PointGrid(reference, lo, hi, cell), repeats)
+    search, _ = timed(lambda: grid.query(query, max_dist), repeats)
+    return {'cell_asked': cell, 'cell': round(grid.grid[3], 6), 'cells': list(grid.grid[4:]), 'ms': whole['ms'],
+            'ms_all': whole['ms_all'], 'build_ms': build['ms'], 'query_ms': search['ms']}, result
 
 
 def equal_within(result, brute, max_dist):

@@ -67,20 +67,20 @@ def one_size(n, repeats, max_dist, brute):
     from monosdf_amd.utils import mesh_align as al
     from monosdf_amd.utils import mesh_args as ma
     from monosdf_amd.utils import mesh_eval as me
+    from monosdf_amd.utils.point_grid import PointGrid
     tgt = bumpy_sphere(n, 1)
     motion = ma.upload(rigid((1.0, 2.0, 3.0), 2.0, (0.012, -0.012, 0.01)))
     src = (bumpy_sphere(n, 2).double() @ motion[:3, :3].T + motion[:3, 3]).float().contiguous()
     out = {'n_source': n, 'n_target': n, 'max_dist': max_dist}
     pivots, t_lo, t_hi = al._pivots('bench_icp', src, tgt)
-    grid = me._grid_over(t_lo, t_hi, max_dist / me.GRID_CELL_FRACTION, me.GRID_MAX_CELLS)
-    out['grid'] = {'cell': round(grid[3], 6), 'cells': list(grid[4:])}
-    out['grid_build'], built = timed(lambda: me._grid_build(tgt, grid), repeats)
+    out['grid_build'], grid = timed(lambda: PointGrid(tgt, t_lo, t_hi, max_dist / me.GRID_CELL_FRACTION), repeats)
+    out['grid'] = {'cell': round(grid.grid[3], 6), 'cells': list(grid.grid[4:])}
     state0 = al._new_state(np.eye(4), 30, src.device)
     state = state0.clone()
     ws = ma.workspace('bench_icp', 'msdf_icp_workspace_bytes', n, device=src.device)
     y = torch.empty_like(src)
     out['transform'], _ = timed(lambda: ma.call('msdf_icp_transform', src, n, state, y), repeats)
-    out['search'], (_, idx) = timed(lambda: me._grid_query_int32(y, built, max_dist), repeats)
+    out['search'], (_, idx) = timed(lambda: grid.query(y, max_dist, int32=True), repeats)
     out['search']['with_neighbour'] = int((idx >= 0).sum())
     out['accumulate'], _ = timed(lambda: ma.call('msdf_icp_accumulate', src, y, tgt, idx, n, n, pivots, state, ws),
                                  repeats)

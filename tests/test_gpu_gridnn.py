@@ -109,6 +109,39 @@ def test_result_does_not_depend_on_the_grid(shells):
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
+def test_one_grid_answers_many_query_sets():
+    """A PointGrid built once over 300 jittered lattice points and queried three times (65, 1 and 130 points: off the
+    64-lane grid on both sides) gives each time, bit for bit, what a fresh nearest_neighbors_within gives and what the
+    numpy brute force gives; queries up to 2 outside the lattice's box have no neighbour within max_dist = 1."""
+    from monosdf_amd.utils import mesh_args as ma
+    from monosdf_amd.utils.point_grid import GRID_CELL_FRACTION, PointGrid
+    rng = np.random.default_rng(21)
+    reference = (gn.lattice(rng)[:300] + rng.uniform(-0.2, 0.2, (300, 3))).astype(np.float32)
+    max_dist = 1.0
+    queries = [rng.uniform(-2.0, 8.0, (n, 3)).astype(np.float32) for n in (65, 1, 130)]
+    queries[1][0] = (3.1, 2.9, 3.2)                            # inside the lattice: it has a neighbour
+    ref = _cuda(reference)
+    _, lo, hi = ma.finite_bounds('test', ref)
+    grid = PointGrid(ref, lo, hi, max_dist / GRID_CELL_FRACTION)
+    assert grid.n_ref == 300 and len(grid.grid) == 7
+    records, starts = grid.records.clone(), grid.starts.clone()
+    found = []
+    for qry in queries:
+        q = _cuda(qry)
+        dist, idx = grid.query(q, max_dist)
+        assert dist.dtype == torch.float32 and idx.dtype == torch.int64 and dist.shape == idx.shape == (len(qry),)
+        fresh = _me().nearest_neighbors_within(ref, q, max_dist)
+        assert torch.equal(idx, fresh[1]) and torch.equal(dist, fresh[0])
+        want = gn.within(*gn.brute(reference, qry), max_dist)
+        assert np.array_equal(idx.cpu().numpy(), want[1])
+        assert np.array_equal(dist.cpu().numpy().view(np.uint32), want[0].view(np.uint32))
+        dist32, idx32 = grid.query(q, max_dist, int32=True)
+        assert idx32.dtype == torch.int32 and torch.equal(idx32.long(), idx) and torch.equal(dist32, dist)
+        found.append((want[1] >= 0).tolist())
+    assert found[1] == [True] and not all(found[0]) and any(found[0]) and not all(found[2]) and any(found[2])
+    assert torch.equal(grid.records, records) and torch.equal(grid.starts, starts)     # a query leaves the grid alone
+
+
 def test_refusals(shells):
     inner, outer, _ = shells
     within = _me().nearest_neighbors_within

@@ -286,6 +286,26 @@ def test_result_does_not_depend_on_the_schedule():
     assert cut[4] == 3 and np.array_equal(cut[3], base[3][:3]) and not np.array_equal(cut[0], base[0])
 
 
+EVALUATION = ['msdf_icp_transform', 'msdf_gnn_cells', 'msdf_gnn_query', 'msdf_icp_accumulate', 'msdf_icp_solve']
+
+
+def test_icp_builds_the_grid_once_and_launches_nothing_else(monkeypatch):
+    """The library calls of one icp(), in order: the target's cells and records once, then five calls per evaluation.
+    The sequence was recorded with this wrapper on the commit before utils/point_grid.py existed."""
+    from monosdf_amd import _lib
+    entries, real = [], _lib.call
+
+    def recording(name, *args):
+        entries.append(name)
+        return real(name, *args)
+    monkeypatch.setattr(_lib, 'call', recording)
+    source, target, _ = inp.case('tiny')
+    evaluations = _al().icp(_cuda(source), _cuda(target), inp.MAX_DIST, max_iteration=3, check_every=1,
+                            return_log=True)[4]
+    assert evaluations == 4
+    assert entries == ['msdf_gnn_cells', 'msdf_gnn_records'] + 4 * EVALUATION
+
+
 def test_far_source_keeps_init():
     source, target, _ = inp.case('tiny')
     init = inp.rigid((1, 1, 0), 3.0, (0.01, 0.0, -0.01))

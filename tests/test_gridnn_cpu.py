@@ -1,9 +1,8 @@
 """CPU tests of the grid-bounded nearest-neighbour search: the numpy restatement of its method (tests/gridnn_numpy.py)
 against the fp32 brute force on every constructed input of the GPU tests, the five mistakes that the small inputs
-catch, the msdf_gnn_* entry points in their header, table and library, and the refusals that need no GPU."""
-import ctypes
+catch, the workspace size and the host-side refusals of the msdf_gnn_* entry points, and the refusals that need no
+GPU."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,7 +14,6 @@ import gridnn_numpy as gn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-GNN_ENTRIES = ('msdf_gnn_workspace_bytes', 'msdf_gnn_cells', 'msdf_gnn_records', 'msdf_gnn_query')
 SMALL = gn.small_cases()
 CATCHERS = ('ring order', 'last ring', 'lattice ties', 'lattice ties, duplicates', '3-4-5')
 
@@ -136,40 +134,13 @@ def test_python_grid_is_the_restatement_grid():
     assert me.GRID_CELL_FRACTION == gn.CELL_FRACTION and me.GRID_MAX_CELLS == gn.MAX_CELLS
 
 
-# ---------------------------------------------------------------- header, table, library
-
-def _prototypes():
-    text = open(os.path.join(ROOT, 'include', 'monosdf_gridnn.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_gnn_entries_declared_in_header_and_table():
-    from monosdf_amd import _lib
-    protos = _prototypes()
-    assert sorted(p[1] for p in protos) == sorted(GNN_ENTRIES) == sorted(_lib._GRIDNN_SIGNATURES)
-    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
-    for ret, name, params in protos:
-        assert name.startswith('msdf_gnn_') and (ret == 'int64_t') == name.endswith('_bytes'), name
-        words = [p.replace('*', ' * ').split() for p in params.split(',')]
-        want = [ctypes.c_void_p if '*' in w else scalars[[x for x in w[:-1] if x != 'const'][0]] for w in words]
-        assert _lib._GRIDNN_SIGNATURES[name] == want, name
-    # the versioned surface is as it was: none of the new names in it, nor in its header
-    assert not [n for n in _lib.exported_symbols() if n.startswith('msdf_gnn_')]
-    assert 'msdf_gnn_' not in open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
-    srcs = [l for l in open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')) if l.startswith('SRCS =')]
-    assert 'gridnn.hip' in srcs[0].split()
-
+# ---------------------------------------------------------------- the library (header and table: test_abi_cpu.py)
 
 def test_library_exports_the_gnn_entries():
     from monosdf_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     lib = _lib.load()
-    for ret, name, _ in _prototypes():
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib._GRIDNN_SIGNATURES[name], name
-        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
     assert lib.msdf_gnn_workspace_bytes(1) == 256 and lib.msdf_gnn_workspace_bytes(1000) == 16000
     assert lib.msdf_gnn_workspace_bytes(0) == -1 and lib.msdf_gnn_workspace_bytes(2 ** 31) == -1
     # argument errors are refused on the host, before any launch

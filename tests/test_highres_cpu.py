@@ -1,12 +1,10 @@
-"""CPU tests of the high-resolution cue merge: the msdf_hrc_* entry points in their header, table, Makefile and
-library; the regenerated inputs (tests/highres_cases.py) against their recorded hashes; the float64 restatement
+"""CPU tests of the high-resolution cue merge: the workspace sizes and the host-side refusals of the msdf_hrc_* entry
+points; the regenerated inputs (tests/highres_cases.py) against their recorded hashes; the float64 restatement
 (tests/highres_numpy.py) against what the reference's own functions returned (tests/golden/highres/*.npz, written by
 scripts/make_golden_highres.py); the conditions on the inputs that give the GPU bars of test_gpu_highres.py their
 meaning; and decode_normals against numpy."""
-import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -19,7 +17,6 @@ import highres_numpy as hn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HRC_ENTRIES = ('msdf_hrc_workspace_bytes', 'msdf_hrc_merge_depth', 'msdf_hrc_merge_normals')
 GAP_CAP = 1e-3                     # every recorded depth gap lies below this: a condition, not a measurement
 
 
@@ -41,46 +38,13 @@ def restated_normals(name):
             for n in range(len(patches))]
 
 
-# ---------------------------------------------------------------- header, table, library
-
-def _prototypes():
-    text = open(os.path.join(ROOT, 'include', 'monosdf_highres.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_highres_entries_declared_in_header_and_table():
-    from monosdf_amd import _lib
-    protos = _prototypes()
-    assert sorted(p[1] for p in protos) == sorted(HRC_ENTRIES) == sorted(_lib._HIGHRES_SIGNATURES)
-    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
-    for ret, name, params in protos:
-        assert name.startswith('msdf_hrc_') and (ret == 'int64_t') == name.endswith('_bytes'), name
-        words = [p.replace('*', ' * ').split() for p in params.split(',')]
-        want = [ctypes.c_void_p if '*' in w else scalars[[x for x in w[:-1] if x != 'const'][0]] for w in words]
-        assert _lib._HIGHRES_SIGNATURES[name] == want, name
-        assert (words[-1][-1] == 'stream') != name.endswith('_bytes'), name
-    # the versioned surface and the other additive tables are as they were
-    assert not [n for n in _lib.exported_symbols() if n.startswith('msdf_hrc_')]
-    others = list(_lib._GRIDNN_SIGNATURES) + list(_lib._MESHCC_SIGNATURES) + list(_lib._OBB_SIGNATURES)
-    assert not [n for n in others if n.startswith('msdf_hrc_')]
-    assert 'msdf_hrc_' not in open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
-    makefile = open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')).read()
-    srcs = [l for l in makefile.splitlines() if l.startswith('SRCS =')]
-    assert 'highres.hip' in srcs[0].split()
-    assert re.search(r'^highres\.o: EXTRA \+= .*-ffp-contract=off', makefile, flags=re.M)
-    assert re.search(r'^highres\.o: .*include/monosdf_highres\.h', makefile, flags=re.M)
-
+# ---------------------------------------------------------------- the library (header and table: test_abi_cpu.py)
 
 def test_library_exports_the_highres_entries():
     from monosdf_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     lib = _lib.load()
-    for ret, name, _ in _prototypes():
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib._HIGHRES_SIGNATURES[name], name
-        assert fn.restype is (ctypes.c_int64 if name.endswith('_bytes') else ctypes.c_int), name
     ws = lib.msdf_hrc_workspace_bytes
     # one image, 1 x 1 patches of 12: no strips; 2 minimum / maximum partials + the pair itself; 256 spare bytes
     assert ws(1, 1, 1, 12, 4, 1) == (4 + 2) * 8 + 256

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_cases import mirrors as _mirrors
 from helpers import Case
 from oracle import config, monosdf_oracle as mo, synth
 
@@ -34,18 +35,6 @@ def test_library_exports_every_declared_symbol():
     assert lib.msdf_abi_version() == _lib.ABI_VERSION == 8
 
 
-def _mirrors():
-    """C struct name -> its ctypes mirror: all fifteen structs of the ABI."""
-    from monosdf_amd import _lib
-    return {'msdf_plan_t': _lib.Plan, 'msdf_layer_t': _lib.Layer, 'msdf_packrule_t': _lib.PackRule,
-            'msdf_wgrad_item_t': _lib.WgradItem, 'msdf_reduce_rule_t': _lib.ReduceRule,
-            'msdf_fg_args_t': _lib.FgArgs, 'msdf_bw_args_t': _lib.BwArgs,
-            'msdf_color_fwd_args_t': _lib.ColorFwdArgs, 'msdf_color_bwd_args_t': _lib.ColorBwdArgs,
-            'msdf_composite_args_t': _lib.CompositeArgs, 'msdf_composite_bwd_args_t': _lib.CompositeBwdArgs,
-            'msdf_sampler_args_t': _lib.SamplerArgs, 'msdf_wn_layer_t': _lib.WnLayer,
-            'msdf_probe_loss_args_t': _lib.ProbeLossArgs, 'msdf_monosdf_loss_args_t': _lib.MonoSdfLossArgs}
-
-
 def test_struct_layouts_match_header():
     """ctypes mirrors of the C structs must have the C compiler's layout: the size of every struct, and the offset and
     size of every field (two swapped fields of one width keep the struct's size)."""
@@ -69,68 +58,6 @@ def test_struct_layouts_match_header():
     for n, f in fields:
         desc = getattr(names[n], f)
         assert (desc.offset, desc.size) == c_side[n + '.' + f], (n, f, desc.offset, desc.size, c_side[n + '.' + f])
-
-
-_C_SCALARS = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'uint32_t': ctypes.c_uint32, 'int64_t': ctypes.c_int64,
-              'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
-# entry points that take a struct pointer as an opaque address: a table in device memory
-_DEVICE_TABLES = {'msdf_pack_weights', 'msdf_weightnorm_forward', 'msdf_weightnorm_backward', 'msdf_wgrad',
-                  'msdf_reduce'}
-
-
-def _prototypes():
-    """(return type, name, parameter text) of every prototype of the header, comments stripped."""
-    text = open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_prototypes_match_the_binding():
-    """Every prototype of the header against _lib._SIGNATURES: the number of arguments, the ctypes type of each and
-    the rule for the return type."""
-    from monosdf_amd import _lib
-    assert ctypes.c_int is ctypes.c_int32
-    protos = _prototypes()
-    assert len(protos) == 64 and sorted(p[1] for p in protos) == _lib.exported_symbols()
-    mirrors, tables = _mirrors(), set()
-    for ret, name, params in protos:
-        params = [p.split() for p in params.replace('*', ' * ').split(',')]
-        params = [] if params == [['void']] else params
-        expected = []
-        for i, words in enumerate(params):
-            words = [w for w in words[:-1] if w != 'const']        # the last word is the parameter's name
-            if words[-1] != '*':
-                assert len(words) == 1, (name, i, words)
-                expected.append((_C_SCALARS[words[0]],))
-            elif words[0] in mirrors:
-                assert len(words) == 2, (name, i, words)
-                expected.append((ctypes.POINTER(mirrors[words[0]]), ctypes.c_void_p))
-            else:
-                assert not words[0].startswith('msdf_'), (name, i, words)      # T*, T* const*: an address
-                expected.append((ctypes.c_void_p,))
-        bound = _lib._SIGNATURES[name]
-        assert len(bound) == len(expected), (name, len(bound), len(expected))
-        for i, (have, want) in enumerate(zip(bound, expected)):
-            assert have in want, (name, i, have, want)
-            if have is ctypes.c_void_p and len(want) == 2:
-                tables.add(name)
-    assert tables == _DEVICE_TABLES
-    for ret, name, _ in protos:                # the rule by which load() chooses the return type
-        assert (ret == 'int64_t') == name.endswith('_bytes'), name
-
-
-def test_loaded_library_has_the_header_return_types():
-    """What load() set on the functions of the library: the header's return type, _SIGNATURES' arguments."""
-    from monosdf_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip('library not built (run python __graft_entry__.py)')
-    lib = _lib.load()
-    protos = _prototypes()
-    assert len(protos) == 64
-    for ret, name, _ in protos:
-        assert getattr(lib, name).restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert getattr(lib, name).argtypes == _lib._SIGNATURES[name], name
 
 
 def test_every_mirror_refuses_an_unknown_field():

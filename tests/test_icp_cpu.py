@@ -1,4 +1,4 @@
-"""CPU tests of the point-to-point ICP: the msdf_icp_* entry points in their header, table and library, the float64
+"""CPU tests of the point-to-point ICP: the sizes and the host-side refusals of the msdf_icp_* entry points, the float64
 restatement (tests/icp_numpy.py) on inputs whose answer is known, the five mistakes it can be made to commit, and the
 conditions on the constructed inputs that the GPU tests (test_gpu_icp.py) rely on."""
 import ctypes
@@ -15,44 +15,10 @@ import icp_numpy as inp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ICP_ENTRIES = ('msdf_icp_state_bytes', 'msdf_icp_workspace_bytes', 'msdf_icp_transform', 'msdf_icp_accumulate',
-               'msdf_icp_solve')
 CASES = ('subset', 'noisy', 'tiny')
 
 
-# ---------------------------------------------------------------- header, table, library
-
-def _prototypes():
-    text = open(os.path.join(ROOT, 'include', 'monosdf_icp.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_icp_entries_declared_in_header_and_table():
-    from monosdf_amd import _lib
-    protos = _prototypes()
-    assert sorted(p[1] for p in protos) == sorted(ICP_ENTRIES) == sorted(_lib._ICP_SIGNATURES)
-    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
-    for ret, name, params in protos:
-        assert name.startswith('msdf_icp_') and (ret == 'int64_t') == name.endswith('_bytes'), name
-        words = [p.replace('*', ' * ').split() for p in params.split(',')]
-        want = [ctypes.c_void_p if '*' in w else scalars[[x for x in w[:-1] if x != 'const'][0]] for w in words]
-        assert _lib._ICP_SIGNATURES[name] == want, name
-        assert (words[-1][-1] == 'stream') != name.endswith('_bytes'), name
-    # the versioned surface and the other additive tables are as they were
-    assert _lib.ABI_VERSION == 8
-    assert not [n for n in _lib.exported_symbols() if n.startswith('msdf_icp_')]
-    others = (list(_lib._GRIDNN_SIGNATURES) + list(_lib._MESHCC_SIGNATURES) + list(_lib._OBB_SIGNATURES) +
-              list(_lib._HIGHRES_SIGNATURES))
-    assert not [n for n in others if n.startswith('msdf_icp_')]
-    for header in ('monosdf_hip.h', 'monosdf_gridnn.h'):
-        assert 'msdf_icp_' not in open(os.path.join(ROOT, 'include', header)).read()
-    makefile = open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')).read()
-    srcs = [l for l in makefile.splitlines() if l.startswith('SRCS =')]
-    assert 'icp.hip' in srcs[0].split()
-    assert re.search(r'^icp\.o: EXTRA \+= .*-ffp-contract=off', makefile, flags=re.M)
-    assert re.search(r'^icp\.o: .*include/monosdf_icp\.h', makefile, flags=re.M)
-
+# ---------------------------------------------------------------- the library (header and table: test_abi_cpu.py)
 
 def test_rotation_solver_has_one_definition():
     csrc = os.path.join(ROOT, 'monosdf_amd', 'csrc')
@@ -72,10 +38,6 @@ def test_library_exports_the_icp_entries():
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     lib = _lib.load()
-    for ret, name, _ in _prototypes():
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib._ICP_SIGNATURES[name], name
-        assert fn.restype is (ctypes.c_int64 if name.endswith('_bytes') else ctypes.c_int), name
     big = 2 ** 31 - 1
     # the state: 18 fp64, two int32 and three fp64 per evaluation; the partials: 17 fp64 per slice of 2048 points
     assert lib.msdf_icp_state_bytes(0) == 152 + 24 and lib.msdf_icp_state_bytes(30) == 152 + 31 * 24

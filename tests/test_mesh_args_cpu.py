@@ -157,3 +157,43 @@ def test_tensor_checks_without_a_gpu():
     with pytest.raises(ValueError, match='f: a on cpu, b on meta'):
         ma.same_device('f', a=a, b=b)
     assert ma.device_of(np.zeros(3), a, None) is None
+
+
+def test_positive_number_takes_what_float_takes_and_refuses_the_rest():
+    from monosdf_amd.utils import mesh_args as ma
+    refused = [(bad, 'positive and finite') for bad in (0, -1.0, float('nan'), float('inf'))]
+    for bad, fragment in refused + [('wide', 'a number'), (None, 'a number')]:
+        for arg in ('cell', 'radius'):
+            with pytest.raises(ValueError, match=r'^radius_thin: %s must be %s, got ' % (arg, fragment)):
+                ma.positive_number('radius_thin', arg, bad)
+    for value, want in ((1, 1.0), (np.float32(2), 2.0), ('3', 3.0)):
+        got = ma.positive_number('f', 'x', value)
+        assert type(got) is float and got == want
+    assert ma.search_distance('f', 20) == 20.0 and type(ma.search_distance('f', 20)) is float
+    with pytest.raises(ValueError, match='^f: max_dist must be finite as a float32'):
+        ma.search_distance('f', 1e39)
+    with pytest.raises(ValueError, match='^f: max_dist must be positive and finite'):
+        ma.search_distance('f', 0)
+
+
+@pytest.mark.parametrize('form', ['host', 'tensor'])
+@pytest.mark.parametrize('with_normals', [False, True])
+def test_kept_mesh_equals_indexing_by_hand(form, with_normals):
+    from monosdf_amd.utils import mesh_args as ma
+    from monosdf_amd.utils.mesh import Mesh
+    rng = np.random.default_rng(5)
+    v = rng.normal(size=(5, 3)).astype(np.float32)
+    n = rng.normal(size=(5, 3))
+    f = np.array([[0, 1, 2], [1, 2, 4], [2, 3, 4]], np.int64)
+    keep = np.array([True, True, True, False, True])
+    faces = ma.compact_faces(torch.from_numpy(keep), torch.from_numpy(f))
+    assert faces.tolist() == [[0, 1, 2], [1, 2, 3]]
+    wrap = torch.from_numpy if form == 'tensor' else (lambda a: a)
+    got = ma.kept_mesh(wrap(v), wrap(n) if with_normals else None, torch.from_numpy(keep), faces)
+    assert isinstance(got, Mesh)
+    for array, dtype in ((got.vertices, np.float64), (got.vertex_normals, np.float64), (got.faces, np.int64)):
+        assert array.dtype == dtype
+    assert np.array_equal(got.vertices, v[[0, 1, 2, 4]].astype(np.float64))
+    assert np.array_equal(got.faces, np.array([[0, 1, 2], [1, 2, 3]]))
+    assert np.array_equal(got.vertex_normals, n[[0, 1, 2, 4]] if with_normals else np.zeros((4, 3)))
+    assert isinstance(ma.host_array(torch.zeros(2)), np.ndarray) and ma.host_array(v) is v

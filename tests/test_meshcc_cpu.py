@@ -1,9 +1,7 @@
 """CPU tests of the mesh connected components: the restatement (tests/meshcc_numpy.py) against scipy on every
-constructed input and every rule, the two rule details that the named cases catch, the msdf_mcc_* entry points in
-their header, table and library, ``aligned_grid``, and the refusals that need no GPU."""
-import ctypes
+constructed input and every rule, the two rule details that the named cases catch, the host-side refusals of the
+msdf_mcc_* entry points, ``aligned_grid``, and the refusals that need no GPU."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,8 +14,6 @@ import meshcc_numpy as cc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MCC_ENTRIES = ('msdf_mcc_edge_keys', 'msdf_mcc_init', 'msdf_mcc_link_edges', 'msdf_mcc_link_vertices',
-               'msdf_mcc_flatten', 'msdf_mcc_segment_sum')
 CASES = {c.name: c for c in cases.all_cases()}
 
 
@@ -72,42 +68,13 @@ def test_sizes_and_selection_restated():
     assert cc.largest(np.array([2.0, 5.0, 5.0])) == 1
 
 
-# ---------------------------------------------------------------- header, table, library
-
-def _prototypes():
-    text = open(os.path.join(ROOT, 'include', 'monosdf_meshcc.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_mcc_entries_declared_in_header_and_table():
-    from monosdf_amd import _lib
-    protos = _prototypes()
-    assert sorted(p[1] for p in protos) == sorted(MCC_ENTRIES) == sorted(_lib._MESHCC_SIGNATURES)
-    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
-    for ret, name, params in protos:
-        assert name.startswith('msdf_mcc_') and (ret == 'int64_t') == name.endswith('_bytes'), name
-        words = [p.replace('*', ' * ').split() for p in params.split(',')]
-        want = [ctypes.c_void_p if '*' in w else scalars[[x for x in w[:-1] if x != 'const'][0]] for w in words]
-        assert _lib._MESHCC_SIGNATURES[name] == want, name
-        assert words[-1][-1] == 'stream', name
-    # the versioned surface and the grid search's table are as they were
-    assert not [n for n in _lib.exported_symbols() if n.startswith('msdf_mcc_')]
-    assert not [n for n in _lib._GRIDNN_SIGNATURES if n.startswith('msdf_mcc_')]
-    assert 'msdf_mcc_' not in open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
-    srcs = [l for l in open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')) if l.startswith('SRCS =')]
-    assert 'meshcc.hip' in srcs[0].split()
-
+# ---------------------------------------------------------------- the library (header and table: test_abi_cpu.py)
 
 def test_library_exports_the_mcc_entries():
     from monosdf_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     lib = _lib.load()
-    for ret, name, _ in _prototypes():
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib._MESHCC_SIGNATURES[name], name
-        assert fn.restype is ctypes.c_int, name
     big = 2 ** 31 - 1
     # per entry: a size of 0 launches nothing (0), a null pointer with a size > 0 and a size outside [0, 2^31) are
     # refused on the host (1)

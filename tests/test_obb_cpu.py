@@ -1,7 +1,6 @@
-"""CPU tests of the oriented bounds: the msdf_obb_* entry points in their header, table and library, the host hull
-(utils/mesh_bounds.HostHull) against scipy, the restatement (tests/obb_numpy.py) on a cuboid whose answer is known,
-and the conditions on the constructed inputs that the GPU tests (test_gpu_obb.py) rely on."""
-import ctypes
+"""CPU tests of the oriented bounds: the workspace size and the host-side refusals of the msdf_obb_* entry points, the
+host hull (utils/mesh_bounds.HostHull) against scipy, the restatement (tests/obb_numpy.py) on a cuboid whose answer is
+known, and the conditions on the constructed inputs that the GPU tests (test_gpu_obb.py) rely on."""
 import os
 import re
 import sys
@@ -16,45 +15,14 @@ import obb_numpy as on
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-OBB_ENTRIES = ('msdf_obb_support_workspace_bytes', 'msdf_obb_support', 'msdf_obb_candidates')
 
-
-# ---------------------------------------------------------------- header, table, library
-
-def _prototypes():
-    text = open(os.path.join(ROOT, 'include', 'monosdf_obb.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    return re.findall(r'^(int|int64_t) (msdf_\w+)\((.*?)\);', text, flags=re.M | re.S)
-
-
-def test_obb_entries_declared_in_header_and_table():
-    from monosdf_amd import _lib
-    protos = _prototypes()
-    assert sorted(p[1] for p in protos) == sorted(OBB_ENTRIES) == sorted(_lib._OBB_SIGNATURES)
-    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double}
-    for ret, name, params in protos:
-        assert name.startswith('msdf_obb_') and (ret == 'int64_t') == name.endswith('_bytes'), name
-        words = [p.replace('*', ' * ').split() for p in params.split(',')]
-        want = [ctypes.c_void_p if '*' in w else scalars[[x for x in w[:-1] if x != 'const'][0]] for w in words]
-        assert _lib._OBB_SIGNATURES[name] == want, name
-        assert (words[-1][-1] == 'stream') != name.endswith('_bytes'), name
-    # the versioned surface and the other additive tables are as they were
-    assert not [n for n in _lib.exported_symbols() if n.startswith('msdf_obb_')]
-    assert not [n for n in list(_lib._GRIDNN_SIGNATURES) + list(_lib._MESHCC_SIGNATURES) if n.startswith('msdf_obb_')]
-    assert 'msdf_obb_' not in open(os.path.join(ROOT, 'include', 'monosdf_hip.h')).read()
-    srcs = [l for l in open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')) if l.startswith('SRCS =')]
-    assert 'obb.hip' in srcs[0].split()
-
+# ---------------------------------------------------------------- the library (header and table: test_abi_cpu.py)
 
 def test_library_exports_the_obb_entries():
     from monosdf_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     lib = _lib.load()
-    for ret, name, _ in _prototypes():
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib._OBB_SIGNATURES[name], name
-        assert fn.restype is (ctypes.c_int64 if name.endswith('_bytes') else ctypes.c_int), name
     # refused on the host, before anything is launched: sizes outside [0, 2^31), null pointers with sizes > 0, a
     # maximum over no points; no planes and no normals launch nothing
     big = 2 ** 31 - 1
