@@ -7,20 +7,8 @@
 // the numpy restatement (tests/refuse_numpy.py) performs, and the rasteriser's edge tests rely on a * b - c * d
 // changing sign exactly when its operands are swapped.
 //
-// Depth rasteriser (raster_*_k).  Parallel over triangles, one lane each, grid.y = view:
-//   * the three vertices go to the camera frame; the two edge vectors are formed in WORLD coordinates (exact to an ulp
-//     of the edge, not of the distance to the camera) and rotated
-//   * per pixel the ray is d = ((j + c - cx) / fx, (i + c - cy) / fy, 1); the side test of edge (p, q) is
-//     d . (p x (q - p)) with p the endpoint of the SMALLER vertex index, negated when the triangle runs the edge the
-//     other way: two triangles that share an edge evaluate the same expression with opposite sign, and `>= 0` (or,
-//     for the other winding, `<= 0`) on all three edges accepts the ray on both sides -- no cracks
-//   * depth z = (n . a) / (n . d) with n the plane normal (from the vertices in ascending index, a the first): ray against plane per pixel, nothing interpolated from
-//     projected vertices, so a triangle that crosses the near plane covers what its visible part covers
-//   * a triangle whose vertices all lie at z >= znear is bounded by the box of its projection (one pixel of slack); one
-//     that crosses z = znear takes the whole image
-//   * a box of at most RASTER_COOP_AREA pixels is scanned by the lane itself (marching-cubes meshes: millions of
-//     triangles of a few pixels); larger boxes are handed round the wave: their set-up is broadcast lane by lane and
-//     all 64 lanes stride over the box, so an image-spanning triangle does not serialise on one lane
+// Depth rasteriser (raster_*_k): the shared triangle rasteriser of raster_core.h (set-up, box walk, wave hand-round,
+// hit test; grid.y = view) with this file's action at an accepted pixel:
 //   * the minimum is kept with a 32-bit unsigned atomicMin on the bits of z (positive floats order as unsigned
 //     integers, as in nn_finish_k); a minimum does not depend on order.  raster_clear_k writes +inf before,
 //     raster_finish_k turns +inf into 0 (background) after.
@@ -30,71 +18,24 @@
 // given; the camera rows are wave-uniform reads, the running mean stays in registers and each voxel is written once.
 // Face rule (tsdf_face_keep_k) and frustum culling (cull_vertices_k): one lane per face / vertex.
 #include "common.h"
+#include "raster_core.h"
 
 namespace {
 
 constexpr int RF_THREADS = 256;
-constexpr int RASTER_COOP_AREA = 256;              // boxes of more pixels than this are scanned by the whole wave
 constexpr unsigned RASTER_INF = 0x7f800000u;       // bits of +inf
 constexpr int64_t RF_MAX = 0x7fffffffll;
 
-struct RasterCam {
-  float fx, fy, cx, cy, pc, znear, zfar;
-  int height, width;
+// the action of the depth image at an accepted pixel: the minimum of the bits of z
+struct DepthMin {
+  unsigned* __restrict__ img;
+  __device__ __forceinline__ void operator()(const TriSetup&, const RasterCam& cam, int i, int j, float z,
+                                             float) const {
+    unsigned* p = img + (size_t)i * (size_t)cam.width + (size_t)j;
+    const unsigned bits = __float_as_uint(z);                           // z > 0: ordered as unsigned
+    if (bits < *p) atomicMin(p, bits);                                  // values only fall: a stale read costs an atomic
+  }
 };
-
-// what the pixel loop needs of one triangle: the three (signed) edge vectors, the plane, the pixel box
-struct TriSetup {
-  float e0x, e0y, e0z, e1x, e1y, e1z, e2x, e2y, e2z;
-  float nx, ny, nz, na;
-  int j0, i0, bw, bh;                               // box: columns j0 .. j0 + bw - 1, rows i0 .. i0 + bh - 1; bw = 0: none
-};
-
-struct V3 {
-  float x, y, z;
-};
-
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) {
-  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-__device__ __forceinline__ V3 rotate(const float* __restrict__ m, V3 v) {
-  return V3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z,
-            m[8] * v.x + m[9] * v.y + m[10] * v.z};
-}
-
-// edge (p -> q) of the triangle, p / q given as world and camera positions with their vertex indices: the vector
-// lo x (hi - lo) of the endpoint pair in ascending index, negated when the triangle runs from hi to lo
-__device__ __forceinline__ V3 edge_vector(const float* __restrict__ m, int ip, V3 wp, V3 cp, int iq, V3 wq, V3 cq) {
-  if (ip == iq) return V3{0.0f, 0.0f, 0.0f};
-  const bool fwd = ip < iq;
-  const V3 wl = fwd ? wp : wq, wh = fwd ? wq : wp, cl = fwd ? cp : cq;
-  const V3 e = cross3(cl, rotate(m, V3{wh.x - wl.x, wh.y - wl.y, wh.z - wl.z}));
-  return fwd ? e : V3{-e.x, -e.y, -e.z};
-}
-
-__device__ __forceinline__ int clamp_to_int(float v, int lo, int hi) {   // NaN -> lo
-  const float c = fminf(fmaxf(v, (float)lo), (float)hi);
-  return (int)c;
-}
-
-__device__ __forceinline__ void raster_pixel(const TriSetup& t, const RasterCam& cam, int i, int j,
-                                             unsigned* __restrict__ img) {
-  const float dx = ((float)j + cam.pc - cam.cx) / cam.fx;
-  const float dy = ((float)i + cam.pc - cam.cy) / cam.fy;
-  const float w0 = dx * t.e0x + dy * t.e0y + t.e0z;
-  const float w1 = dx * t.e1x + dy * t.e1y + t.e1z;
-  const float w2 = dx * t.e2x + dy * t.e2y + t.e2z;
-  const bool in = (w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f) || (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);
-  if (!in) return;
-  const float nd = dx * t.nx + dy * t.ny + t.nz;
-  if (nd == 0.0f) return;
-  const float z = t.na / nd;
-  if (!(z >= cam.znear && z <= cam.zfar)) return;                      // NaN fails
-  unsigned* p = img + (size_t)i * (size_t)cam.width + (size_t)j;
-  const unsigned bits = __float_as_uint(z);                             // z > 0: ordered as unsigned
-  if (bits < *p) atomicMin(p, bits);                                    // values only fall: a stale read costs an atomic
-}
 
 __global__ void __launch_bounds__(RF_THREADS)
 raster_clear_k(unsigned* __restrict__ img, int64_t n) {
@@ -115,92 +56,7 @@ raster_tri_k(const float* __restrict__ verts, int64_t V, const int32_t* __restri
   const float* __restrict__ m = w2c + 12 * (size_t)view;
   unsigned* __restrict__ img = depth + (size_t)view * (size_t)cam.height * (size_t)cam.width;
   const int64_t f = (int64_t)blockIdx.x * RF_THREADS + threadIdx.x;
-
-  TriSetup t;
-  t.bw = 0;
-  t.bh = 0;
-  if (f < F) {
-    const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-    if (ia >= 0 && ib >= 0 && ic >= 0 && ia < V && ib < V && ic < V) {
-      const V3 wa{verts[3 * (size_t)ia], verts[3 * (size_t)ia + 1], verts[3 * (size_t)ia + 2]};
-      const V3 wb{verts[3 * (size_t)ib], verts[3 * (size_t)ib + 1], verts[3 * (size_t)ib + 2]};
-      const V3 wc{verts[3 * (size_t)ic], verts[3 * (size_t)ic + 1], verts[3 * (size_t)ic + 2]};
-      V3 a = rotate(m, wa), b = rotate(m, wb), c = rotate(m, wc);
-      a = V3{a.x + m[3], a.y + m[7], a.z + m[11]};
-      b = V3{b.x + m[3], b.y + m[7], b.z + m[11]};
-      c = V3{c.x + m[3], c.y + m[7], c.z + m[11]};
-      const float zmin = fminf(a.z, fminf(b.z, c.z)), zmax = fmaxf(a.z, fmaxf(b.z, c.z));
-      // every intersection lies between the vertices' depths
-      if (zmax >= cam.znear && zmin <= cam.zfar) {
-        const V3 e0 = edge_vector(m, ia, wa, a, ib, wb, b);
-        const V3 e1 = edge_vector(m, ib, wb, b, ic, wc, c);
-        const V3 e2 = edge_vector(m, ic, wc, c, ia, wa, a);
-        // the plane from the vertices in ascending index, so that every rotation and winding of the face gives the
-        // same bits of z
-        int s0 = ia, s1 = ib, s2 = ic;
-        V3 p0 = wa, p1 = wb, p2 = wc, q0 = a;
-        if (s1 < s0) {
-          const int ti = s0; s0 = s1; s1 = ti;
-          const V3 tp = p0; p0 = p1; p1 = tp;
-          q0 = b;
-        }
-        if (s2 < s1) {
-          const int ti = s1; s1 = s2; s2 = ti;
-          const V3 tp = p1; p1 = p2; p2 = tp;
-          if (s1 < s0) {
-            const int tj = s0; s0 = s1; s1 = tj;
-            const V3 tq = p0; p0 = p1; p1 = tq;
-            q0 = c;
-          }
-        }
-        const V3 n = cross3(rotate(m, V3{p1.x - p0.x, p1.y - p0.y, p1.z - p0.z}),
-                            rotate(m, V3{p2.x - p0.x, p2.y - p0.y, p2.z - p0.z}));
-        t.e0x = e0.x, t.e0y = e0.y, t.e0z = e0.z;
-        t.e1x = e1.x, t.e1y = e1.y, t.e1z = e1.z;
-        t.e2x = e2.x, t.e2y = e2.y, t.e2z = e2.z;
-        t.nx = n.x, t.ny = n.y, t.nz = n.z;
-        t.na = n.x * q0.x + n.y * q0.y + n.z * q0.z;
-        int j0 = 0, j1 = cam.width - 1, i0 = 0, i1 = cam.height - 1;
-        if (zmin >= cam.znear) {                                        // znear > 0: the projections exist
-          const float ua = cam.fx * a.x / a.z, ub = cam.fx * b.x / b.z, uc = cam.fx * c.x / c.z;
-          const float va = cam.fy * a.y / a.z, vb = cam.fy * b.y / b.z, vc = cam.fy * c.y / c.z;
-          const float off_u = cam.cx - cam.pc, off_v = cam.cy - cam.pc;  // pixel j has its centre at u = j - off_u
-          j0 = clamp_to_int(floorf(fminf(ua, fminf(ub, uc)) + off_u) - 1.0f, 0, cam.width);
-          j1 = clamp_to_int(ceilf(fmaxf(ua, fmaxf(ub, uc)) + off_u) + 1.0f, -1, cam.width - 1);
-          i0 = clamp_to_int(floorf(fminf(va, fminf(vb, vc)) + off_v) - 1.0f, 0, cam.height);
-          i1 = clamp_to_int(ceilf(fmaxf(va, fmaxf(vb, vc)) + off_v) + 1.0f, -1, cam.height - 1);
-        }
-        if (j1 >= j0 && i1 >= i0 && !(n.x == 0.0f && n.y == 0.0f && n.z == 0.0f)) {
-          t.j0 = j0, t.i0 = i0, t.bw = j1 - j0 + 1, t.bh = i1 - i0 + 1;
-        }
-      }
-    }
-  }
-
-  const int area = t.bw * t.bh;                                         // <= height * width < 2^31 (checked by the host)
-  const bool large = area > RASTER_COOP_AREA;
-  if (area > 0 && !large) {
-    for (int i = t.i0; i < t.i0 + t.bh; ++i)
-      for (int j = t.j0; j < t.j0 + t.bw; ++j) raster_pixel(t, cam, i, j, img);
-  }
-  // the large boxes of this wave, one after the other, by all its lanes
-  unsigned long long todo = __ballot(large);
-  const int lane = lane_id();
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    TriSetup s;
-    s.e0x = __shfl(t.e0x, src, 64), s.e0y = __shfl(t.e0y, src, 64), s.e0z = __shfl(t.e0z, src, 64);
-    s.e1x = __shfl(t.e1x, src, 64), s.e1y = __shfl(t.e1y, src, 64), s.e1z = __shfl(t.e1z, src, 64);
-    s.e2x = __shfl(t.e2x, src, 64), s.e2y = __shfl(t.e2y, src, 64), s.e2z = __shfl(t.e2z, src, 64);
-    s.nx = __shfl(t.nx, src, 64), s.ny = __shfl(t.ny, src, 64), s.nz = __shfl(t.nz, src, 64);
-    s.na = __shfl(t.na, src, 64);
-    s.j0 = __shfl(t.j0, src, 64), s.i0 = __shfl(t.i0, src, 64);
-    s.bw = __shfl(t.bw, src, 64), s.bh = __shfl(t.bh, src, 64);
-    const unsigned n_px = (unsigned)(s.bw * s.bh), bw = (unsigned)s.bw;
-    for (unsigned k = (unsigned)lane; k < n_px; k += 64u)
-      raster_pixel(s, cam, s.i0 + (int)(k / bw), s.j0 + (int)(k % bw), img);
-  }
+  raster_triangle(verts, V, faces, F, f, m, cam, DepthMin{img});
 }
 
 struct TsdfArgs {

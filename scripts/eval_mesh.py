@@ -1,6 +1,7 @@
 """Metrics of a reconstructed mesh against a ground-truth mesh, on the GPU, as one JSON line.
 
     python scripts/eval_mesh.py PRED.ply GT.ply --protocol scannet|replica [--scale-mat cameras.npz] [--crop] [--align]
+                                         [--depth-l1 [--unseen FILE.npy] [--n-imgs N]]
     python scripts/eval_mesh.py PRED.ply --protocol dtu --dtu-dir DTU --scan 24 [--cameras cameras.npz --masks DIR|NPY]
                                          [--search brute|grid]
 
@@ -17,6 +18,10 @@ world frame (evaluation/eval.py applies it before it writes the mesh; pass it wh
 (monosdf_amd/utils/mesh_align.py; parity with open3d's ICP is unverified); without it the meshes must be aligned
 already.  --crop (replica) then crops PRED to the oriented bounding box of GT scaled by 1.05, as calc_3d_metric() always
 does (monosdf_amd/utils/mesh_bounds.py); without it PRED is scored as it came.
+--depth-l1 (replica) adds `depth_l1_cm`, the 2D metric of calc_2d_metric(): both meshes rendered from --n-imgs (1000)
+random views inside the room, redrawn while they see a point of --unseen (the scene's `*_pc_unseen.npy`), mean absolute
+depth difference in centimetres (monosdf_amd/utils/mesh_render.py; parity with open3d's renderer is unverified).  With
+--align PRED is aligned for it as for the 3D metrics.  Without the flag the output is unchanged.
 The reference scores the re-fused (ScanNet) or frustum-culled (Replica) mesh: make PRED.ply with scripts/refuse_mesh.py.
 """
 import argparse
@@ -69,8 +74,16 @@ def main():
                     help='replica: crop PRED to the oriented bounding box of GT scaled by 1.05 first')
     ap.add_argument('--align', action='store_true',
                     help='replica: move PRED onto GT by point-to-point ICP on the vertices first')
+    ap.add_argument('--depth-l1', action='store_true',
+                    help='replica: add the depth L1 of calc_2d_metric() in centimetres')
+    ap.add_argument('--unseen', default=None, help='replica, --depth-l1: .npy cloud no view may see')
+    ap.add_argument('--n-imgs', type=int, default=1000, help='replica, --depth-l1: views')
     args = ap.parse_args()
     from monosdf_amd.utils import mesh_eval
+    if args.depth_l1 and args.protocol != 'replica':
+        ap.error('--depth-l1 belongs to --protocol replica')
+    if (args.unseen is not None or args.n_imgs != 1000) and not args.depth_l1:
+        ap.error('--unseen and --n-imgs belong to --depth-l1')
     if args.crop and args.protocol != 'replica':
         ap.error('--crop belongs to --protocol replica')
     if args.align and args.protocol != 'replica':
@@ -88,6 +101,11 @@ def main():
     else:
         out = mesh_eval.evaluate_replica(pred, gt, n_samples=args.n_samples, dist_th=args.threshold, seed=args.seed,
                                            crop=args.crop, align=args.align)
+        if args.depth_l1:
+            from monosdf_amd.utils import mesh_render
+            out['depth_l1_cm'] = mesh_render.evaluate_depth_l1(
+                pred, gt, n_imgs=args.n_imgs, unseen=None if args.unseen is None else np.load(args.unseen),
+                align=args.align, seed=args.seed)
     print(json.dumps(out))
 
 
