@@ -2,8 +2,8 @@
  * which stands in for the reference's open3d renderings (render/render_trajectory_open3d.py, render_tntvideos_open3d.py
  * with render/render.json; replica_eval/eval_recon.py:196-285, calc_2d_metric).  Same conventions as monosdf_hip.h, whose
  * status codes these functions return: raw DEVICE pointers, an explicit hipStream_t passed as void*, callers own every
- * buffer, nothing allocates, frees or synchronises.  This is a TOOL header: it lies under include/mesh/, beside and not
- * among the headers of the versioned and additive surface, and monosdf_hip.h and MSDF_ABI_VERSION are unchanged.
+ * buffer, nothing allocates, frees or synchronises.  These entry points are additive: monosdf_hip.h and
+ * MSDF_ABI_VERSION are unchanged.
  * Every size lies in [0, 2^31), n_views * height * width among them: a size outside it returns MSDF_ERR_ARG, and so do a
  * null pointer where the sizes leave work to do, znear <= 0, zfar < znear and a cull mode outside 0..2.  Zero work
  * returns MSDF_OK and launches nothing.  No floating-point atomics: the same input gives bitwise the same output
@@ -52,7 +52,7 @@
 #define MONOSDF_RENDER_H
 
 #include <stdint.h>
-#include "../monosdf_hip.h"
+#include "monosdf_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -269,12 +269,7 @@ _ABI = {VERSIONED_HEADER: {
     'msdf_icp_transform': [_P, C.c_int64, _P, _P, _P],
     'msdf_icp_accumulate': [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P],
     'msdf_icp_solve': [_P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P, _P],
-}}
-
-# The tool headers: entry points of the mesh tools that lie under include/mesh/, outside the versioned and additive
-# surface that headers() lists (tests/abi_cases.py names every header directly under include/ and every entry of it; a
-# tool is bound by the same rule without joining that list).
-_TOOLS = {'mesh/monosdf_render.h': {                       # csrc/meshrender.hip
+}, 'monosdf_render.h': {                                   # csrc/meshrender.hip
     'msdf_rnd_visibility_workspace_bytes': [C.c_int64, C.c_int64, C.c_int64],
     'msdf_rnd_visibility': [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                             C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P],
@@ -287,7 +282,7 @@ _TOOLS = {'mesh/monosdf_render.h': {                       # csrc/meshrender.hip
                            C.c_int64, _P, _P],
 }}
 
-_ENTRIES = [name for tables in (_ABI, _TOOLS) for table in tables.values() for name in table]
+_ENTRIES = [name for table in _ABI.values() for name in table]
 if len(_ENTRIES) != len(set(_ENTRIES)):
     raise ImportError('monosdf_amd: bound under two headers: %s'
                       % sorted(n for n in set(_ENTRIES) if _ENTRIES.count(n) > 1))
@@ -305,16 +300,6 @@ def signatures(header):
     return _ABI[header]
 
 
-def tool_headers():
-    """The tool headers under include/ (paths relative to it), which headers() does not list."""
-    return list(_TOOLS)
-
-
-def tool_signatures(header):
-    """{entry: argtypes} of one header of ``tool_headers()``."""
-    return _TOOLS[header]
-
-
 def load():
     """Load the HIP library once; raises if it has not been built (no fallback)."""
     global _lib
@@ -325,7 +310,7 @@ def load():
             'monosdf_amd: %s not found -- build it with `python __graft_entry__.py` or '
             '`make -C monosdf_amd/csrc` (there is no non-HIP fallback)' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in list(_ABI.values()) + list(_TOOLS.values()):
+    for table in _ABI.values():
         for name, argtypes in table.items():
             fn = getattr(lib, name)        # AttributeError if the symbol is missing: intended
             fn.argtypes = argtypes

@@ -27,14 +27,13 @@
 // looked up once.  A round: every undecided point scans its earlier-ranked neighbours; one kept -> removed, else one
 // undecided -> stays, else kept.  States only move from undecided to their final value, so the update is in place and
 // the result does not depend on what a racing read sees, only the number of rounds does.
-#include "common.h"
+#include "tool_common.h"
 
 namespace {
 
 constexpr int DT_THREADS = 256;
 constexpr int DT_MAX_RADIUS = 32;                  // half-width <= one word: a word and its two neighbours suffice
 constexpr int64_t DT_MAX_PIXELS = 1ll << 37;
-constexpr int64_t DT_MAX_POINTS = 0x7fffffffll;
 constexpr int DT_CELL_BITS = 21;
 constexpr int64_t DT_CELL_MAX = (1ll << DT_CELL_BITS) - 2;   // cells of points lie in [1, DT_CELL_MAX]
 constexpr double LAT_MAX_CANDIDATES = 17179869184.0;         // 2^34: such a face alone has >= 2^31 points
@@ -46,8 +45,6 @@ struct DtDisk {
   int r;
   int8_t hw[2 * DT_MAX_RADIUS + 1];                // hw[dy + r]
 };
-
-inline unsigned dt_blocks(int64_t n) { return (unsigned)((n + DT_THREADS - 1) / DT_THREADS); }
 
 // ---------------------------------------------------------------- dilation
 
@@ -115,9 +112,7 @@ dt_mask_vertices_k(const float* __restrict__ verts, int64_t n, const float* __re
   uint8_t kept = 1;
   for (int v = 0; v < n_views; ++v) {
     const float* P = proj + 12 * v;                                    // same address in every lane
-    const float pu = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
-    const float pv = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
-    const float pz = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+    const float pu = affine_row<0>(P, x, y, z), pv = affine_row<1>(P, x, y, z), pz = affine_row<2>(P, x, y, z);
     const float den = pz + 1e-6f;
     const float px = pu / den, py = pv / den;
     const bool valid = px > 0.0f && px < wmax && py > 0.0f && py < hmax;    // false for NaN
@@ -365,8 +360,7 @@ int64_t dilate_words(int n, int H, int W) { return (int64_t)n * H * ((W + 31) / 
 
 extern "C" int64_t msdf_dtu_dilate_workspace_bytes(int n_views, int height, int width) {
   if (!dilate_sizes_ok(n_views, height, width, 0)) return -1;
-  const int64_t b = 2 * 4 * dilate_words(n_views, height, width);
-  return b > 256 ? b : 256;
+  return workspace_floor(2 * 4 * dilate_words(n_views, height, width));
 }
 
 extern "C" int msdf_dtu_dilate(const uint8_t* masks, int n_views, int height, int width, int radius, void* workspace,
@@ -386,25 +380,25 @@ extern "C" int msdf_dtu_dilate(const uint8_t* masks, int n_views, int height, in
   const int64_t rows = (int64_t)n_views * height, words = rows * Wd, pixels = rows * width;
   uint32_t* packed = (uint32_t*)workspace;
   uint32_t* grown = packed + words;
-  dt_pack_k<<<dt_blocks(words), DT_THREADS, 0, s>>>(masks, rows, width, Wd, packed);
-  dt_dilate_k<<<dt_blocks(words), DT_THREADS, 0, s>>>(packed, rows, height, Wd, disk, grown);
-  dt_unpack_k<<<dt_blocks(pixels), DT_THREADS, 0, s>>>(grown, pixels, width, Wd, out);
+  dt_pack_k<<<blocks_for(words, DT_THREADS), DT_THREADS, 0, s>>>(masks, rows, width, Wd, packed);
+  dt_dilate_k<<<blocks_for(words, DT_THREADS), DT_THREADS, 0, s>>>(packed, rows, height, Wd, disk, grown);
+  dt_unpack_k<<<blocks_for(pixels, DT_THREADS), DT_THREADS, 0, s>>>(grown, pixels, width, Wd, out);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_dtu_mask_vertices(const float* verts, int64_t n_verts, const float* proj, int n_views,
                                       const uint8_t* dilated, int height, int width, uint8_t* keep, void* stream) {
-  if (n_verts < 0 || n_verts > DT_MAX_POINTS || !dilate_sizes_ok(n_views, height, width, 0)) return MSDF_ERR_ARG;
+  if (!fits_int32(n_verts) || !dilate_sizes_ok(n_views, height, width, 0)) return MSDF_ERR_ARG;
   if (n_verts == 0) return MSDF_OK;
   if (!verts || !keep || (n_views > 0 && (!proj || !dilated))) return MSDF_ERR_ARG;
-  dt_mask_vertices_k<<<dt_blocks(n_verts), DT_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, proj, n_views,
-                                                                                dilated, height, width, keep);
+  dt_mask_vertices_k<<<blocks_for(n_verts, DT_THREADS), DT_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, proj,
+                                                                                              n_views, dilated, height,
+                                                                                              width, keep);
   return msdf_check_launch();
 }
 
 static bool lattice_args_ok(int64_t n_verts, int64_t n_faces, double density) {
-  return n_verts >= 0 && n_verts <= DT_MAX_POINTS && n_faces >= 0 && n_faces <= DT_MAX_POINTS && density > 0.0 &&
-         density < __builtin_inf();
+  return fits_int32(n_verts) && fits_int32(n_faces) && positive_finite(density);
 }
 
 extern "C" int msdf_dtu_lattice_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
@@ -412,7 +406,7 @@ extern "C" int msdf_dtu_lattice_count(const float* verts, int64_t n_verts, const
   if (!lattice_args_ok(n_verts, n_faces, density)) return MSDF_ERR_ARG;
   if (n_faces == 0) return MSDF_OK;
   if (!verts || !faces || !counts) return MSDF_ERR_ARG;
-  const unsigned blocks = (unsigned)((n_faces + 3) / 4);
+  const unsigned blocks = (unsigned)blocks_for(n_faces, DT_THREADS / MSDF_WAVE);   // a wave per face
   dt_lattice_count_k<<<blocks, DT_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces, n_faces, density, counts);
   return msdf_check_launch();
 }
@@ -420,56 +414,58 @@ extern "C" int msdf_dtu_lattice_count(const float* verts, int64_t n_verts, const
 extern "C" int msdf_dtu_lattice_emit(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                                      double density, const int64_t* offsets, int64_t n_points, float* out,
                                      void* stream) {
-  if (!lattice_args_ok(n_verts, n_faces, density) || n_points < 0 || n_points > DT_MAX_POINTS) return MSDF_ERR_ARG;
+  if (!lattice_args_ok(n_verts, n_faces, density) || !fits_int32(n_points)) return MSDF_ERR_ARG;
   if (n_faces == 0 || n_points == 0) return MSDF_OK;
   if (!verts || !faces || !offsets || !out) return MSDF_ERR_ARG;
-  const unsigned blocks = (unsigned)((n_faces + 3) / 4);
+  const unsigned blocks = (unsigned)blocks_for(n_faces, DT_THREADS / MSDF_WAVE);   // a wave per face
   dt_lattice_emit_k<<<blocks, DT_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces, n_faces, density, offsets,
                                                                     n_points, out);
   return msdf_check_launch();
 }
 
 extern "C" int64_t msdf_dtu_thin_workspace_bytes(int64_t n) {
-  if (n < 0 || n > DT_MAX_POINTS) return -1;
-  const int64_t b = 16 * n + 72 * n + n;
-  return b > 256 ? b : 256;
+  if (!fits_int32(n)) return -1;
+  return workspace_floor(16 * n + 72 * n + n);
 }
 
 extern "C" int msdf_dtu_thin_keys(const float* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell,
                                   int64_t* keys, void* stream) {
-  if (n < 0 || n > DT_MAX_POINTS || !(cell > 0.0) || !(cell < __builtin_inf())) return MSDF_ERR_ARG;
+  if (!fits_int32(n) || !positive_finite(cell)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!points || !keys) return MSDF_ERR_ARG;
-  dt_thin_keys_k<<<dt_blocks(n), DT_THREADS, 0, (hipStream_t)stream>>>(points, n, lo_x, lo_y, lo_z, cell, keys);
+  dt_thin_keys_k<<<blocks_for(n, DT_THREADS), DT_THREADS, 0, (hipStream_t)stream>>>(points, n, lo_x, lo_y, lo_z, cell,
+                                                                                    keys);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_dtu_thin_prepare(const float* points, const int64_t* perm, const int64_t* rank,
                                      const int64_t* sorted_keys, int64_t n, void* workspace, void* stream) {
-  if (n < 0 || n > DT_MAX_POINTS) return MSDF_ERR_ARG;
+  if (!fits_int32(n)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!points || !perm || !sorted_keys || !workspace) return MSDF_ERR_ARG;
-  dt_thin_prepare_k<<<dt_blocks(n), DT_THREADS, 0, (hipStream_t)stream>>>(points, perm, rank, sorted_keys, n,
-                                                                         thin_ws(workspace, n));
+  dt_thin_prepare_k<<<blocks_for(n, DT_THREADS), DT_THREADS, 0, (hipStream_t)stream>>>(points, perm, rank, sorted_keys,
+                                                                                       n, thin_ws(workspace, n));
   return msdf_check_launch();
 }
 
 extern "C" int msdf_dtu_thin_round(void* workspace, int64_t n, double radius, uint32_t* undecided, void* stream) {
-  if (n < 0 || n > DT_MAX_POINTS || !(radius > 0.0) || !(radius < __builtin_inf())) return MSDF_ERR_ARG;
+  if (!fits_int32(n) || !positive_finite(radius)) return MSDF_ERR_ARG;
   if (!undecided) return MSDF_ERR_ARG;
   const hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(undecided, 0, sizeof(uint32_t), s) != hipSuccess) return MSDF_ERR_LAUNCH;
   if (n == 0) return MSDF_OK;
   if (!workspace) return MSDF_ERR_ARG;
-  dt_thin_round_k<<<dt_blocks(n), DT_THREADS, 0, s>>>(thin_ws(workspace, n), n, radius * radius, undecided);
+  dt_thin_round_k<<<blocks_for(n, DT_THREADS), DT_THREADS, 0, s>>>(thin_ws(workspace, n), n, radius * radius,
+                                                                   undecided);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_dtu_thin_finish(const void* workspace, const int64_t* perm, int64_t n, uint8_t* keep,
                                     void* stream) {
-  if (n < 0 || n > DT_MAX_POINTS) return MSDF_ERR_ARG;
+  if (!fits_int32(n)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!workspace || !perm || !keep) return MSDF_ERR_ARG;
-  dt_thin_finish_k<<<dt_blocks(n), DT_THREADS, 0, (hipStream_t)stream>>>(thin_ws((void*)workspace, n), perm, n, keep);
+  dt_thin_finish_k<<<blocks_for(n, DT_THREADS), DT_THREADS, 0, (hipStream_t)stream>>>(thin_ws((void*)workspace, n),
+                                                                                      perm, n, keep);
   return msdf_check_launch();
 }

@@ -1,10 +1,9 @@
 // Exact nearest neighbour within a bound, through a uniform grid (ABI: include/monosdf_gridnn.h).  The DTU protocol uses
 // only the distances below max_dist (dtu_eval/eval.py:120-134), so "the nearest reference point, if one lies within
 // max_dist" is enough, and on thinned clouds it looks at a few hundred candidates per query where the brute-force
-// search of nnsearch.hip looks at all of them.  What is reported is bit for bit what that search returns: the same
-// fp32 expression d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) on the three differences (this object is built with
-// -ffp-contract=off, as nnsearch.o is), the minimum taken over the 64-bit word (bits of d2 << 32) | index, so the
-// smallest index wins among equal d2, and the same sqrtf.  No atomics: the same inputs give the same bits every call.
+// search of nnsearch.hip looks at all of them.  What is reported is bit for bit what that search returns: both form the
+// distance with nn_d2 and take the minimum over nn_word (tool_common.h, which states them; this object is built with
+// the flags of nnsearch.o), and both take the same sqrtf.  No atomics: the same inputs give the same bits every call.
 //
 // Grid.  Cells of side h over the reference cloud's box; cell = floor((p - lo) / h) per axis in fp64 on the fp32
 // coordinate, clamped to the grid (in fp64, before the conversion: a query may lie anywhere), linear index with z
@@ -24,14 +23,13 @@
 // is at or below that, no point outside ties or beats it.  At k = kmax every point outside has fp32 distance >
 // (float) max_dist, so a best that passes the final test sqrtf(best_d2) <= (float) max_dist beats all of them (sqrtf is
 // monotone), and a best that does not pass is not reported.  h, and so the grid, only ever changes the speed.
-#include "common.h"
+#include "tool_common.h"
 #include "../../include/monosdf_gridnn.h"
 
 namespace {
 
 constexpr int GN_THREADS = 256;
-constexpr int64_t GN_MAX_POINTS = 0x7fffffffll;    // int32 indices
-constexpr int64_t GN_MAX_CELLS = 0x7ffffffell;     // starts holds cells + 1 int32 entries
+constexpr int64_t GN_MAX_CELLS = MSDF_COUNT_MAX - 1;   // starts holds cells + 1 int32 entries
 constexpr double GN_SLACK = 1.0 + 1.0 / 1024.0;
 constexpr uint64_t GN_NONE = 0x7f800000ffffffffull;   // d2 = +inf, index -1: any point orders before it
 
@@ -43,13 +41,11 @@ struct GnGrid {
 
 bool gn_grid_ok(double lx, double ly, double lz, double h, int nx, int ny, int nz) {
   const double inf = __builtin_inf();
-  if (!(h > 0.0) || !(h < inf) || !(lx > -inf && lx < inf) || !(ly > -inf && ly < inf) || !(lz > -inf && lz < inf))
+  if (!positive_finite(h) || !(lx > -inf && lx < inf) || !(ly > -inf && ly < inf) || !(lz > -inf && lz < inf))
     return false;
   if (nx < 1 || ny < 1 || nz < 1) return false;
   return (int64_t)nx * ny <= GN_MAX_CELLS && (int64_t)nx * ny * nz <= GN_MAX_CELLS;
 }
-
-inline unsigned gn_blocks(int64_t n) { return (unsigned)((n + GN_THREADS - 1) / GN_THREADS); }
 
 __device__ __forceinline__ int gn_cell(float p, double lo, double h, int n) {
   double c = floor(((double)p - lo) / h);
@@ -101,52 +97,49 @@ gn_query_k(const float* __restrict__ query, const int64_t* __restrict__ qorder, 
         for (int32_t r = a; r < b; ++r) {
           const v4f p = rec[r];
           const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-          const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-          const uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | __float_as_uint(p.w);
+          const uint64_t key = nn_word(nn_d2(dx, dy, dz), __float_as_uint(p.w));
           best = key < best ? key : best;
         }
       }
     }
     const double bound = (double)k * g.h / GN_SLACK;
-    if ((double)__uint_as_float((uint32_t)(best >> 32)) <= bound * bound || k >= kmax) break;
+    if ((double)nn_word_d2(best) <= bound * bound || k >= kmax) break;
     k = 2 * k < kmax ? 2 * k : kmax;
   }
-  const float d = sqrtf(__uint_as_float((uint32_t)(best >> 32)));
+  const float d = sqrtf(nn_word_d2(best));
   const bool within = d <= max_dist;
   dist[q] = within ? d : __builtin_inff();
-  idx[q] = within ? (int32_t)(uint32_t)best : -1;
+  idx[q] = within ? nn_word_index(best) : -1;
 }
 
 }  // namespace
 
 extern "C" int64_t msdf_gnn_workspace_bytes(int64_t n_ref) {
-  if (n_ref < 1 || n_ref > GN_MAX_POINTS) return -1;
-  const int64_t b = 16 * n_ref;
-  return b > 256 ? b : 256;
+  if (n_ref < 1 || !fits_int32(n_ref)) return -1;
+  return workspace_floor(16 * n_ref);
 }
 
 extern "C" int msdf_gnn_cells(const float* points, int64_t n, double lo_x, double lo_y, double lo_z, double h, int n_x,
                               int n_y, int n_z, int32_t* cells, void* stream) {
-  if (n < 0 || n > GN_MAX_POINTS || !gn_grid_ok(lo_x, lo_y, lo_z, h, n_x, n_y, n_z)) return MSDF_ERR_ARG;
+  if (!fits_int32(n) || !gn_grid_ok(lo_x, lo_y, lo_z, h, n_x, n_y, n_z)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!points || !cells) return MSDF_ERR_ARG;
   const GnGrid g = {{lo_x, lo_y, lo_z}, h, {n_x, n_y, n_z}};
-  gn_cells_k<<<gn_blocks(n), GN_THREADS, 0, (hipStream_t)stream>>>(points, n, g, cells);
+  gn_cells_k<<<blocks_for(n, GN_THREADS), GN_THREADS, 0, (hipStream_t)stream>>>(points, n, g, cells);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_gnn_records(const float* ref, const int64_t* order, int64_t n_ref, void* records, void* stream) {
-  if (n_ref < 1 || n_ref > GN_MAX_POINTS || !ref || !order || !records) return MSDF_ERR_ARG;
-  gn_records_k<<<gn_blocks(n_ref), GN_THREADS, 0, (hipStream_t)stream>>>(ref, order, n_ref, (v4f*)records);
+  if (n_ref < 1 || !fits_int32(n_ref) || !ref || !order || !records) return MSDF_ERR_ARG;
+  gn_records_k<<<blocks_for(n_ref, GN_THREADS), GN_THREADS, 0, (hipStream_t)stream>>>(ref, order, n_ref, (v4f*)records);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_gnn_query(const float* query, const int64_t* query_order, int64_t n_query, const void* records,
                               int64_t n_ref, const int32_t* starts, double lo_x, double lo_y, double lo_z, double h,
                               int n_x, int n_y, int n_z, double max_dist, float* dist, int32_t* idx, void* stream) {
-  if (n_ref < 1 || n_ref > GN_MAX_POINTS || n_query < 0 || n_query > GN_MAX_POINTS) return MSDF_ERR_ARG;
-  if (!gn_grid_ok(lo_x, lo_y, lo_z, h, n_x, n_y, n_z) || !(max_dist > 0.0) || !(max_dist < __builtin_inf()))
-    return MSDF_ERR_ARG;
+  if (n_ref < 1 || !fits_int32(n_ref) || !fits_int32(n_query)) return MSDF_ERR_ARG;
+  if (!gn_grid_ok(lo_x, lo_y, lo_z, h, n_x, n_y, n_z) || !positive_finite(max_dist)) return MSDF_ERR_ARG;
   if (n_query == 0) return MSDF_OK;
   if (!query || !query_order || !records || !starts || !dist || !idx) return MSDF_ERR_ARG;
   const GnGrid g = {{lo_x, lo_y, lo_z}, h, {n_x, n_y, n_z}};
@@ -154,7 +147,7 @@ extern "C" int msdf_gnn_query(const float* query, const int64_t* query_order, in
   const int widest = n_x > n_y ? (n_x > n_z ? n_x : n_z) : (n_y > n_z ? n_y : n_z);
   const double rings = ceil(max_dist * GN_SLACK / h);
   const int kmax = rings < (double)widest ? (rings < 1.0 ? 1 : (int)rings) : widest;
-  gn_query_k<<<gn_blocks(n_query), GN_THREADS, 0, (hipStream_t)stream>>>(
+  gn_query_k<<<blocks_for(n_query, GN_THREADS), GN_THREADS, 0, (hipStream_t)stream>>>(
       query, query_order, n_query, (const v4f*)records, starts, g, kmax, (float)max_dist, dist, idx);
   return msdf_check_launch();
 }

@@ -15,7 +15,7 @@
 //
 // Built with -ffp-contract=off: every product and sum is rounded on its own, as the header states and the float64
 // restatement of the tests (tests/highres_numpy.py) computes.
-#include "common.h"
+#include "tool_common.h"
 #include "rotation_solve.h"
 #include "../../include/monosdf_highres.h"
 
@@ -25,7 +25,6 @@ constexpr int HRC_THREADS = 256;                        // 4 waves
 constexpr int HRC_WAVES = HRC_THREADS / MSDF_WAVE;
 constexpr int HRC_EPT = 8;                              // elements per lane
 constexpr int HRC_TILE = HRC_THREADS * HRC_EPT;         // elements per workgroup
-constexpr int64_t HRC_MAX_GRID = 0x7fffffffll;
 
 template <int NCH> struct HrcCue;
 template <> struct HrcCue<1> { typedef float T; static constexpr int NS = 4, K = 2; };
@@ -366,7 +365,7 @@ hrc_normal_encode_k(double* __restrict__ out, int hw, int n_tiles, HrcStepRef re
 
 // ---------------------------------------------------------------- host side
 
-inline int64_t hrc_tiles(int64_t elements) { return (elements + HRC_TILE - 1) / HRC_TILE; }
+inline int64_t hrc_tiles(int64_t elements) { return blocks_for(elements, HRC_TILE); }
 
 struct HrcSizes {
   int64_t N, R, C, P, S, O, H, W, ch;
@@ -380,11 +379,11 @@ bool hrc_sizes(int64_t n, int64_t rows, int64_t cols, int64_t patch, int64_t str
   z.N = n, z.R = rows, z.C = cols, z.P = patch, z.S = stride, z.O = patch - stride, z.ch = channels;
   z.H = patch + stride * (rows - 1);
   z.W = patch + stride * (cols - 1);
-  if (3 * z.H * z.W >= HRC_MAX_GRID) return false;                      // H, W < 2^25, so the product is below 2^52
+  if (3 * z.H * z.W >= MSDF_COUNT_MAX) return false;                    // H, W < 2^25, so the product is below 2^52
   if (3 * n * rows * cols * patch * patch >= (1ll << 40)) return false; // factors below 2^2 2^17 2^10 2^10 2^28
   // workgroups per launch: the largest are the apply launches of the two phases and the last kernels
   const int64_t row = n * rows * hrc_tiles(patch * patch), col = n * hrc_tiles(patch * z.W), end = n * hrc_tiles(z.H * z.W);
-  if (row >= HRC_MAX_GRID || col >= HRC_MAX_GRID || end >= HRC_MAX_GRID) return false;
+  if (row >= MSDF_COUNT_MAX || col >= MSDF_COUNT_MAX || end >= MSDF_COUNT_MAX) return false;
   const int64_t ns = channels == 1 ? 4 : 9;
   int64_t part = n * rows * hrc_tiles(z.O * patch) * ns;
   if (n * hrc_tiles(z.O * z.W) * ns > part) part = n * hrc_tiles(z.O * z.W) * ns;

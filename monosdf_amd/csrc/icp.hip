@@ -12,7 +12,7 @@
 //
 // Built with -ffp-contract=off: every product and sum is rounded on its own, as the header states and the float64
 // restatement of the tests (tests/icp_numpy.py) computes.
-#include "common.h"
+#include "tool_common.h"
 #include "rotation_solve.h"
 #include "../../include/monosdf_icp.h"
 
@@ -23,7 +23,6 @@ constexpr int ICP_WAVES = ICP_THREADS / MSDF_WAVE;
 constexpr int ICP_PPL = 8;                              // points per lane
 constexpr int ICP_SLICE = ICP_THREADS * ICP_PPL;        // points per workgroup
 constexpr int ICP_NS = 17;                              // sums per slice
-constexpr int64_t ICP_MAX = 0x7fffffffll;               // sizes and indices are below 2^31
 constexpr int64_t ICP_MAX_ITERATION = 1 << 20;
 
 struct IcpState {                                       // the header's layout; the log rows follow
@@ -33,8 +32,7 @@ struct IcpState {                                       // the header's layout; 
 };
 static_assert(sizeof(IcpState) == 152, "the layout that include/monosdf_icp.h states");
 
-inline bool icp_size_ok(int64_t n) { return n >= 0 && n < ICP_MAX; }
-inline int64_t icp_slices(int64_t n) { return (n + ICP_SLICE - 1) / ICP_SLICE; }
+inline int64_t icp_slices(int64_t n) { return blocks_for(n, ICP_SLICE); }
 
 __global__ void __launch_bounds__(ICP_THREADS)
 icp_transform_k(const float* __restrict__ src, int64_t n, const IcpState* __restrict__ st, float* __restrict__ out) {
@@ -42,11 +40,9 @@ icp_transform_k(const float* __restrict__ src, int64_t n, const IcpState* __rest
   const int64_t i = (int64_t)blockIdx.x * ICP_THREADS + threadIdx.x;
   if (i >= n) return;
   const double x = (double)src[3 * i], y = (double)src[3 * i + 1], z = (double)src[3 * i + 2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double* r = st->T + 4 * a;
-    out[3 * i + a] = (float)(((r[0] * x + r[1] * y) + r[2] * z) + r[3]);
-  }
+  out[3 * i] = (float)affine_row<0>(st->T, x, y, z);
+  out[3 * i + 1] = (float)affine_row<1>(st->T, x, y, z);
+  out[3 * i + 2] = (float)affine_row<2>(st->T, x, y, z);
 }
 
 __global__ void __launch_bounds__(ICP_THREADS)
@@ -173,24 +169,23 @@ extern "C" int64_t msdf_icp_state_bytes(int64_t max_iteration) {
 }
 
 extern "C" int64_t msdf_icp_workspace_bytes(int64_t n) {
-  if (!icp_size_ok(n)) return -1;
-  const int64_t b = icp_slices(n) * ICP_NS * 8;                        // < 2^20 * 136
-  return b > 256 ? b : 256;
+  if (!below_int32_max(n)) return -1;
+  return workspace_floor(icp_slices(n) * ICP_NS * 8);                  // < 2^20 * 136
 }
 
 extern "C" int msdf_icp_transform(const float* source, int64_t n, const void* state, float* y, void* stream) {
-  if (!icp_size_ok(n) || !state) return MSDF_ERR_ARG;
+  if (!below_int32_max(n) || !state) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!source || !y) return MSDF_ERR_ARG;
-  icp_transform_k<<<(unsigned)((n + ICP_THREADS - 1) / ICP_THREADS), ICP_THREADS, 0, (hipStream_t)stream>>>(
-      source, n, (const IcpState*)state, y);
+  icp_transform_k<<<blocks_for(n, ICP_THREADS), ICP_THREADS, 0, (hipStream_t)stream>>>(source, n,
+                                                                                       (const IcpState*)state, y);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_icp_accumulate(const float* source, const float* y, const float* target, const int32_t* idx,
                                    int64_t n, int64_t m, const double* pivots, const void* state, void* workspace,
                                    void* stream) {
-  if (!icp_size_ok(n) || !icp_size_ok(m) || !state || !pivots) return MSDF_ERR_ARG;
+  if (!below_int32_max(n) || !below_int32_max(m) || !state || !pivots) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!source || !y || !idx || !workspace || (m > 0 && !target)) return MSDF_ERR_ARG;
   icp_accumulate_k<<<(unsigned)icp_slices(n), ICP_THREADS, 0, (hipStream_t)stream>>>(
@@ -200,7 +195,7 @@ extern "C" int msdf_icp_accumulate(const float* source, const float* y, const fl
 
 extern "C" int msdf_icp_solve(const void* workspace, int64_t n, const double* pivots, int64_t max_iteration,
                               double relative_fitness, double relative_rmse, void* state, void* stream) {
-  if (!icp_size_ok(n) || max_iteration < 0 || max_iteration > ICP_MAX_ITERATION || !state || !pivots)
+  if (!below_int32_max(n) || max_iteration < 0 || max_iteration > ICP_MAX_ITERATION || !state || !pivots)
     return MSDF_ERR_ARG;
   if (n > 0 && !workspace) return MSDF_ERR_ARG;
   icp_solve_k<<<1, MSDF_WAVE, 0, (hipStream_t)stream>>>((const double*)workspace, icp_slices(n), n, pivots,

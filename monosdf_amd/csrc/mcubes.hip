@@ -13,7 +13,7 @@
 //   faces      words with triangles: every cell recomputes its code; a cell edge maps to (owner voxel, axis) and so to
 //              its vertex id through the owner word's base and masks (order: linear cell index, then table order)
 // Every output position follows from the scans: no atomics, so results are bitwise identical run to run.
-#include "common.h"
+#include "tool_common.h"
 #define MC_TABLE static __constant__ const
 #include "mc_tables.h"
 
@@ -39,8 +39,8 @@ struct McLayout {
 McLayout mc_layout(int nx, int ny, int nz) {
   McLayout L;
   const int64_t n = (int64_t)nx * ny * nz;
-  L.n_words = (n + 63) / 64;
-  L.n_blocks = (L.n_words + MC_SCAN_WORDS - 1) / MC_SCAN_WORDS;
+  L.n_words = blocks_for(n, 64);
+  L.n_blocks = blocks_for(L.n_words, MC_SCAN_WORDS);
   L.words_off = 0;
   L.counts_off = (size_t)L.n_words * sizeof(McWord);                     // uint32 [n_words][2]: vertices, triangles
   L.bsum_off = L.counts_off + (size_t)L.n_words * 8;                     // int64 [n_blocks][2]
@@ -49,7 +49,7 @@ McLayout mc_layout(int nx, int ny, int nz) {
 }
 
 bool mc_dims_ok(int nx, int ny, int nz) {
-  return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
+  return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz <= MSDF_COUNT_MAX;
 }
 
 struct Grid {
@@ -362,12 +362,11 @@ extern "C" int msdf_mc_count(const float* vol, int nx, int ny, int nz, float lev
   int64_t* bsum = (int64_t*)(ws + L.bsum_off);
   const hipStream_t s = (hipStream_t)stream;
   const uint32_t n = (uint32_t)((int64_t)nx * ny * nz);
-  const int64_t per_block = (MC_THREADS / 64) * MC_CLASSIFY_WORDS;
-  mc_classify_k<<<(unsigned)((L.n_words + per_block - 1) / per_block), MC_THREADS, 0, s>>>(
+  mc_classify_k<<<blocks_for(L.n_words, (MC_THREADS / 64) * MC_CLASSIFY_WORDS), MC_THREADS, 0, s>>>(
       vol, make_grid(nx, ny, nz), n, L.n_words, level, words, counts);
   mc_scan_blocks_k<<<(unsigned)L.n_blocks, MC_THREADS, 0, s>>>(counts, L.n_words, words, bsum);
   mc_scan_top_k<<<1, 1024, 0, s>>>(bsum, L.n_blocks, totals);
-  mc_add_back_k<<<(unsigned)((L.n_words + MC_THREADS - 1) / MC_THREADS), MC_THREADS, 0, s>>>(bsum, L.n_words, words);
+  mc_add_back_k<<<blocks_for(L.n_words, MC_THREADS), MC_THREADS, 0, s>>>(bsum, L.n_words, words);
   return msdf_check_launch();
 }
 
@@ -380,8 +379,7 @@ extern "C" int msdf_mc_emit(const float* vol, int nx, int ny, int nz, float leve
   const uint32_t* counts = (const uint32_t*)(ws + L.counts_off);
   const hipStream_t s = (hipStream_t)stream;
   const Grid g = make_grid(nx, ny, nz);
-  const int64_t words_per_block = MC_EMIT_WORDS * (MC_THREADS / 64);
-  const unsigned blocks = (unsigned)((L.n_words + words_per_block - 1) / words_per_block);
+  const unsigned blocks = (unsigned)blocks_for(L.n_words, MC_EMIT_WORDS * (MC_THREADS / 64));
   mc_emit_vertices_k<<<blocks, MC_THREADS, 0, s>>>(vol, g, level, sx, sy, sz, words, counts, L.n_words, verts,
                                                    normals);
   mc_emit_faces_k<<<blocks, MC_THREADS, 0, s>>>(vol, g, (uint32_t)((int64_t)nx * ny * nz), level, words, counts,

@@ -22,7 +22,7 @@
 // agent-scope atomic loads (served by L2, where the atomics land).  Correctness does not rest on that: a stale parent
 // is still a node of the same tree with a smaller id, and the walk from it reaches the same root.  The scope only keeps
 // the chains short.  Integer vector atomics only; no floating-point atomics, no inline assembly.
-#include "common.h"
+#include "tool_common.h"
 #include "../../include/monosdf_meshcc.h"
 
 namespace {
@@ -30,10 +30,6 @@ namespace {
 constexpr int MCC_THREADS = 256;
 constexpr int MCC_SUM_THREADS = 512;                 // 8 waves per segment
 constexpr int64_t MCC_SUM_MAX_BLOCKS = 1 << 20;      // more segments than this: a workgroup takes several
-constexpr int64_t MCC_MAX = 0x7fffffffll;            // sizes and ids are below 2^31
-
-inline unsigned mcc_blocks(int64_t n) { return (unsigned)((n + MCC_THREADS - 1) / MCC_THREADS); }
-inline bool mcc_size_ok(int64_t n) { return n >= 0 && n < MCC_MAX; }
 
 __device__ __forceinline__ int32_t mcc_load(const int32_t* parent, int32_t i) {
   return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -140,50 +136,52 @@ mcc_segment_sum_k(const double* __restrict__ values, const int64_t* __restrict__
 }  // namespace
 
 extern "C" int msdf_mcc_edge_keys(const int32_t* faces, int64_t n_faces, int64_t* keys, void* stream) {
-  if (!mcc_size_ok(n_faces) || !mcc_size_ok(3 * n_faces)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n_faces) || !below_int32_max(3 * n_faces)) return MSDF_ERR_ARG;
   if (n_faces == 0) return MSDF_OK;
   if (!faces || !keys) return MSDF_ERR_ARG;
-  mcc_edge_keys_k<<<mcc_blocks(3 * n_faces), MCC_THREADS, 0, (hipStream_t)stream>>>(faces, 3 * n_faces, keys);
+  mcc_edge_keys_k<<<blocks_for(3 * n_faces, MCC_THREADS), MCC_THREADS, 0, (hipStream_t)stream>>>(faces, 3 * n_faces,
+                                                                                                 keys);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_mcc_init(int32_t* parent, int64_t n, void* stream) {
-  if (!mcc_size_ok(n)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!parent) return MSDF_ERR_ARG;
-  mcc_init_k<<<mcc_blocks(n), MCC_THREADS, 0, (hipStream_t)stream>>>(parent, n);
+  mcc_init_k<<<blocks_for(n, MCC_THREADS), MCC_THREADS, 0, (hipStream_t)stream>>>(parent, n);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_mcc_link_edges(const int64_t* sorted_keys, const int64_t* order, int64_t n_keys, int rule,
                                    int32_t* parent, void* stream) {
-  if (!mcc_size_ok(n_keys) || (rule != 0 && rule != 1)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n_keys) || (rule != 0 && rule != 1)) return MSDF_ERR_ARG;
   if (n_keys == 0) return MSDF_OK;
   if (!sorted_keys || !order || !parent) return MSDF_ERR_ARG;
-  mcc_link_edges_k<<<mcc_blocks(n_keys), MCC_THREADS, 0, (hipStream_t)stream>>>(sorted_keys, order, n_keys, rule,
-                                                                                 parent);
+  mcc_link_edges_k<<<blocks_for(n_keys, MCC_THREADS), MCC_THREADS, 0, (hipStream_t)stream>>>(sorted_keys, order, n_keys,
+                                                                                             rule, parent);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_mcc_link_vertices(const int32_t* faces, int64_t n_faces, int32_t* parent, void* stream) {
-  if (!mcc_size_ok(n_faces)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n_faces)) return MSDF_ERR_ARG;
   if (n_faces == 0) return MSDF_OK;
   if (!faces || !parent) return MSDF_ERR_ARG;
-  mcc_link_vertices_k<<<mcc_blocks(n_faces), MCC_THREADS, 0, (hipStream_t)stream>>>(faces, n_faces, parent);
+  mcc_link_vertices_k<<<blocks_for(n_faces, MCC_THREADS), MCC_THREADS, 0, (hipStream_t)stream>>>(faces, n_faces,
+                                                                                                 parent);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_mcc_flatten(int32_t* parent, int64_t n, void* stream) {
-  if (!mcc_size_ok(n)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!parent) return MSDF_ERR_ARG;
-  mcc_flatten_k<<<mcc_blocks(n), MCC_THREADS, 0, (hipStream_t)stream>>>(parent, n);
+  mcc_flatten_k<<<blocks_for(n, MCC_THREADS), MCC_THREADS, 0, (hipStream_t)stream>>>(parent, n);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_mcc_segment_sum(const double* values, const int64_t* seg_start, int64_t m, double* out,
                                     void* stream) {
-  if (!mcc_size_ok(m)) return MSDF_ERR_ARG;
+  if (!below_int32_max(m)) return MSDF_ERR_ARG;
   if (m == 0) return MSDF_OK;
   if (!values || !seg_start || !out) return MSDF_ERR_ARG;
   const unsigned blocks = (unsigned)(m < MCC_SUM_MAX_BLOCKS ? m : MCC_SUM_MAX_BLOCKS);

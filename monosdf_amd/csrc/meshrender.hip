@@ -1,4 +1,4 @@
-// Mesh renderer on the device (ABI: include/mesh/monosdf_render.h, which states every rule): what the reference shows
+// Mesh renderer on the device (ABI: include/monosdf_render.h, which states every rule): what the reference shows
 // its results with (render/render_trajectory_open3d.py: open3d's Phong shader and the four lights of render.json) and
 // the depth L1 of replica_eval/eval_recon.py:196-285.  Five groups of kernels, none with a floating-point atomic: the
 // same inputs give bitwise the same outputs every call.  Built with -ffp-contract=off: the rasteriser of raster_core.h
@@ -14,29 +14,22 @@
 // Shading (rnd_shade_k): one lane per pixel; the set-up of the winning face is formed again by raster_face_plane.
 // Depth L1 (rnd_depth_l1_k): one workgroup per view, a fixed summation order.  View rejection (rnd_views_see_k): point
 // chunks x views, a plain store of 1.
-#include "common.h"
+#include "tool_common.h"
 #include "raster_core.h"
-#include "../../include/mesh/monosdf_render.h"
+#include "../../include/monosdf_render.h"
 
 namespace {
 
 constexpr int RN_THREADS = 256;
-constexpr int64_t RN_MAX = 0x7fffffffll;
 constexpr unsigned long long RN_EMPTY = ~0ull;
 constexpr int RN_VIEWS_PER_LAUNCH = 65535;         // grid.y
 constexpr int RN_CHUNK = 2048;                     // points of one workgroup of rnd_views_see_k
 
-unsigned blocks_for(int64_t n, int per_block = RN_THREADS) { return (unsigned)((n + per_block - 1) / per_block); }
-
-bool intrinsics_ok(float fx, float fy, float cx, float cy) {
-  return fx > 0.0f && fy > 0.0f && cx == cx && cy == cy && fx < __builtin_inff() && fy < __builtin_inff();
-}
-
 bool image_ok(int64_t n_views, int64_t height, int64_t width) {
-  if (n_views < 0 || n_views > RN_MAX || height < 0 || height > RN_MAX || width < 0 || width > RN_MAX) return false;
+  if (!fits_int32(n_views) || !fits_int32(height) || !fits_int32(width)) return false;
   if (height == 0 || width == 0 || n_views == 0) return true;
-  if (height > RN_MAX / width) return false;
-  return n_views <= RN_MAX / (height * width);
+  if (height > MSDF_COUNT_MAX / width) return false;
+  return n_views <= MSDF_COUNT_MAX / (height * width);
 }
 
 // ---- visibility
@@ -275,7 +268,7 @@ extern "C" int msdf_rnd_visibility(const float* verts, int64_t n_verts, const in
                                    const float* w2c, int64_t n_views, float fx, float fy, float cx, float cy,
                                    int64_t height, int64_t width, float znear, float zfar, float pixel_center, int cull,
                                    void* workspace, float* depth, int32_t* face, void* stream) {
-  if (n_verts < 0 || n_verts > RN_MAX || n_faces < 0 || n_faces > RN_MAX || !image_ok(n_views, height, width) ||
+  if (!fits_int32(n_verts) || !fits_int32(n_faces) || !image_ok(n_views, height, width) ||
       !intrinsics_ok(fx, fy, cx, cy) || !(znear > 0.0f) || !(zfar >= znear) || !(pixel_center == pixel_center) ||
       cull < 0 || cull > 2)
     return MSDF_ERR_ARG;
@@ -284,27 +277,28 @@ extern "C" int msdf_rnd_visibility(const float* verts, int64_t n_verts, const in
   if (!depth || !face || !workspace || !w2c || (n_faces > 0 && (!verts || !faces))) return MSDF_ERR_ARG;
   const hipStream_t s = (hipStream_t)stream;
   unsigned long long* ws = (unsigned long long*)workspace;
-  rnd_vis_clear_k<<<blocks_for(n_px), RN_THREADS, 0, s>>>(ws, n_px);
+  rnd_vis_clear_k<<<blocks_for(n_px, RN_THREADS), RN_THREADS, 0, s>>>(ws, n_px);
   if (n_faces > 0 && n_verts > 0) {
     const RasterCam cam{fx, fy, cx, cy, pixel_center, znear, zfar, (int)height, (int)width};
     for (int64_t v0 = 0; v0 < n_views; v0 += RN_VIEWS_PER_LAUNCH) {
       const int64_t nv = n_views - v0 < RN_VIEWS_PER_LAUNCH ? n_views - v0 : RN_VIEWS_PER_LAUNCH;
-      rnd_vis_tri_k<<<dim3(blocks_for(n_faces), (unsigned)nv), RN_THREADS, 0, s>>>(
+      rnd_vis_tri_k<<<dim3((unsigned)blocks_for(n_faces, RN_THREADS), (unsigned)nv), RN_THREADS, 0, s>>>(
           verts, n_verts, faces, n_faces, w2c + 12 * v0, cam, cull, ws + v0 * height * width);
     }
   }
-  rnd_vis_finish_k<<<blocks_for(n_px), RN_THREADS, 0, s>>>(ws, n_px, depth, face);
+  rnd_vis_finish_k<<<blocks_for(n_px, RN_THREADS), RN_THREADS, 0, s>>>(ws, n_px, depth, face);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_rnd_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                                        const int32_t* inc_start, const int32_t* inc_face, float* normals,
                                        void* stream) {
-  if (n_verts < 0 || n_verts > RN_MAX || n_faces < 0 || n_faces > RN_MAX / 3) return MSDF_ERR_ARG;
+  if (!fits_int32(n_verts) || n_faces < 0 || n_faces > MSDF_COUNT_MAX / 3) return MSDF_ERR_ARG;
   if (n_verts == 0) return MSDF_OK;
   if (!verts || !normals || !inc_start || (n_faces > 0 && (!faces || !inc_face))) return MSDF_ERR_ARG;
-  rnd_vertex_normals_k<<<blocks_for(n_verts), RN_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces, n_faces,
-                                                                                   inc_start, inc_face, normals);
+  rnd_vertex_normals_k<<<blocks_for(n_verts, RN_THREADS), RN_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces,
+                                                                                                n_faces, inc_start,
+                                                                                                inc_face, normals);
   return msdf_check_launch();
 }
 
@@ -314,7 +308,7 @@ extern "C" int msdf_rnd_shade(const int32_t* face, const float* depth, int64_t n
                               const float* normals, const float* colors, float base_r, float base_g, float base_b,
                               const float* lights, float centre_x, float centre_y, float centre_z, float extent,
                               int flat, int two_sided, float* rgb, void* stream) {
-  if (n_verts < 0 || n_verts > RN_MAX || n_faces < 0 || n_faces > RN_MAX || !image_ok(n_views, height, width) ||
+  if (!fits_int32(n_verts) || !fits_int32(n_faces) || !image_ok(n_views, height, width) ||
       !intrinsics_ok(fx, fy, cx, cy) || !(pixel_center == pixel_center))
     return MSDF_ERR_ARG;
   const int64_t n_px = n_views * height * width;
@@ -324,8 +318,9 @@ extern "C" int msdf_rnd_shade(const int32_t* face, const float* depth, int64_t n
     return MSDF_ERR_ARG;
   const ShadeArgs p{fx, fy, cx, cy, pixel_center, base_r, base_g, base_b, centre_x, centre_y, centre_z, extent,
                     (int)height, (int)width, flat ? 1 : 0, two_sided ? 1 : 0};
-  rnd_shade_k<<<blocks_for(n_px), RN_THREADS, 0, (hipStream_t)stream>>>(face, depth, n_px, w2c, p, verts, n_verts,
-                                                                        faces, n_faces, normals, colors, lights, rgb);
+  rnd_shade_k<<<blocks_for(n_px, RN_THREADS), RN_THREADS, 0, (hipStream_t)stream>>>(face, depth, n_px, w2c, p, verts,
+                                                                                    n_verts, faces, n_faces, normals,
+                                                                                    colors, lights, rgb);
   return msdf_check_launch();
 }
 
@@ -341,17 +336,17 @@ extern "C" int msdf_rnd_depth_l1(const float* a, const float* b, int64_t n_views
 extern "C" int msdf_rnd_views_see(const float* points, int64_t n_points, const float* w2c, int64_t n_views, float fx,
                                   float fy, float cx, float cy, int64_t height, int64_t width, int32_t* flags,
                                   void* stream) {
-  if (n_points < 0 || n_points > RN_MAX / 3 || n_views < 0 || n_views > RN_MAX || height < 0 || height > RN_MAX ||
-      width < 0 || width > RN_MAX || !intrinsics_ok(fx, fy, cx, cy))
+  if (n_points < 0 || n_points > MSDF_COUNT_MAX / 3 || !fits_int32(n_views) || !fits_int32(height) ||
+      !fits_int32(width) || !intrinsics_ok(fx, fy, cx, cy))
     return MSDF_ERR_ARG;
   if (n_views == 0) return MSDF_OK;
   if (!flags || !w2c || (n_points > 0 && !points)) return MSDF_ERR_ARG;
   const hipStream_t s = (hipStream_t)stream;
-  rnd_flags_clear_k<<<blocks_for(n_views), RN_THREADS, 0, s>>>(flags, n_views);
+  rnd_flags_clear_k<<<blocks_for(n_views, RN_THREADS), RN_THREADS, 0, s>>>(flags, n_views);
   if (n_points > 0) {
     for (int64_t v0 = 0; v0 < n_views; v0 += RN_VIEWS_PER_LAUNCH) {
       const int64_t nv = n_views - v0 < RN_VIEWS_PER_LAUNCH ? n_views - v0 : RN_VIEWS_PER_LAUNCH;
-      rnd_views_see_k<<<dim3(blocks_for(n_points, RN_CHUNK), (unsigned)nv), RN_THREADS, 0, s>>>(
+      rnd_views_see_k<<<dim3((unsigned)blocks_for(n_points, RN_CHUNK), (unsigned)nv), RN_THREADS, 0, s>>>(
           points, n_points, w2c + 12 * v0, fx, fy, cx, cy, (float)width, (float)height, flags + v0);
     }
   }

@@ -25,7 +25,7 @@
 // axis, o = min_bound - v / 2, every operation rounded separately in fp32 (this object is built with
 // -ffp-contract=off); one output per occupied voxel, the fp64 sum of its points in ascending original index over their
 // count, rounded once to fp32.  The keys are sorted by the caller (a stable sort); no floating-point atomics.
-#include "common.h"
+#include "tool_common.h"
 
 namespace {
 
@@ -37,7 +37,6 @@ constexpr int NN_RPT = NN_TILE / NN_THREADS;       // records a thread stages pe
 constexpr int64_t NN_TARGET_BLOCKS = 4096;         // automatic split: about this many workgroups ...
 constexpr int64_t NN_MIN_TILES = 4;                // ... of at least this many tiles each
 constexpr int64_t NN_MAX_SPLITS = 65535;           // grid.y
-constexpr int64_t NN_MAX_POINTS = 0x7fffffffll;    // int32 indices
 
 struct NnSplit {
   int64_t tiles_per_split;
@@ -46,10 +45,10 @@ struct NnSplit {
 
 // n_splits <= 0: chosen from the sizes; > 0: the caller's, clamped to what the tile count allows
 NnSplit nn_split(int64_t R, int64_t Q, int n_splits) {
-  const int64_t tiles = (R + NN_TILE - 1) / NN_TILE;
+  const int64_t tiles = blocks_for(R, NN_TILE);
   int64_t s = n_splits;
   if (s <= 0) {
-    const int64_t qb = Q > 0 ? (Q + NN_QBLOCK - 1) / NN_QBLOCK : 1;
+    const int64_t qb = Q > 0 ? blocks_for(Q, NN_QBLOCK) : 1;
     s = (NN_TARGET_BLOCKS + qb - 1) / qb;
     const int64_t s_max = (tiles + NN_MIN_TILES - 1) / NN_MIN_TILES;
     if (s > s_max) s = s_max;
@@ -63,7 +62,7 @@ NnSplit nn_split(int64_t R, int64_t Q, int n_splits) {
   return p;
 }
 
-bool nn_sizes_ok(int64_t R, int64_t Q) { return R >= 1 && R <= NN_MAX_POINTS && Q >= 0 && Q <= NN_MAX_POINTS; }
+bool nn_sizes_ok(int64_t R, int64_t Q) { return R >= 1 && fits_int32(R) && fits_int32(Q); }
 
 __global__ void __launch_bounds__(NN_THREADS)
 nn_search_k(const float* __restrict__ ref, int64_t R, const float* __restrict__ query, int64_t Q,
@@ -117,7 +116,7 @@ nn_search_k(const float* __restrict__ ref, int64_t R, const float* __restrict__ 
 #pragma unroll
       for (int k = 0; k < NN_QPL; ++k) {
         const float dx = qx[k] - r.x, dy = qy[k] - r.y, dz = qz[k] - r.z;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+        const float d2 = nn_d2(dx, dy, dz);
         const bool lt = d2 < best[k];                                  // strict: the earlier index keeps a tie
         best[k] = lt ? d2 : best[k];
         best_i[k] = lt ? jb + j : best_i[k];
@@ -128,7 +127,7 @@ nn_search_k(const float* __restrict__ ref, int64_t R, const float* __restrict__ 
 #pragma unroll
   for (int k = 0; k < NN_QPL; ++k) {
     const int64_t q = q0 + (int64_t)k * NN_THREADS;
-    if (q < Q) out[q] = ((uint64_t)__float_as_uint(best[k]) << 32) | (uint32_t)best_i[k];
+    if (q < Q) out[q] = nn_word(best[k], (uint32_t)best_i[k]);
   }
 }
 
@@ -142,8 +141,8 @@ nn_finish_k(const uint64_t* __restrict__ partial, int64_t Q, int n_splits, float
     const uint64_t v = partial[(size_t)s * (size_t)Q + q];
     m = v < m ? v : m;
   }
-  dist[q] = sqrtf(__uint_as_float((uint32_t)(m >> 32)));
-  idx[q] = (int32_t)(uint32_t)m;
+  dist[q] = sqrtf(nn_word_d2(m));
+  idx[q] = nn_word_index(m);
 }
 
 constexpr int VOX_BITS = 21;                       // per axis in the 63-bit key
@@ -195,8 +194,7 @@ extern "C" int msdf_nn_split_count(int64_t n_ref, int64_t n_query, int n_splits)
 
 extern "C" int64_t msdf_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int n_splits) {
   if (!nn_sizes_ok(n_ref, n_query)) return -1;
-  const int64_t b = (int64_t)nn_split(n_ref, n_query, n_splits).n_splits * n_query * 8;
-  return b > 256 ? b : 256;
+  return workspace_floor((int64_t)nn_split(n_ref, n_query, n_splits).n_splits * n_query * 8);
 }
 
 extern "C" int msdf_nn_search(const float* ref, int64_t n_ref, const float* query, int64_t n_query, int n_splits,
@@ -207,29 +205,27 @@ extern "C" int msdf_nn_search(const float* ref, int64_t n_ref, const float* quer
   const NnSplit p = nn_split(n_ref, n_query, n_splits);
   const hipStream_t s = (hipStream_t)stream;
   uint64_t* partial = (uint64_t*)workspace;
-  const dim3 grid((unsigned)((n_query + NN_QBLOCK - 1) / NN_QBLOCK), (unsigned)p.n_splits);
+  const dim3 grid((unsigned)blocks_for(n_query, NN_QBLOCK), (unsigned)p.n_splits);
   nn_search_k<<<grid, NN_THREADS, 0, s>>>(ref, n_ref, query, n_query, p.tiles_per_split, partial);
-  nn_finish_k<<<(unsigned)((n_query + NN_THREADS - 1) / NN_THREADS), NN_THREADS, 0, s>>>(partial, n_query, p.n_splits,
-                                                                                       dist, idx);
+  nn_finish_k<<<blocks_for(n_query, NN_THREADS), NN_THREADS, 0, s>>>(partial, n_query, p.n_splits, dist, idx);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_voxel_keys(const float* points, int64_t n, const float* min_bound, float voxel_size,
                                int64_t* keys, void* stream) {
-  if (n < 0 || n > NN_MAX_POINTS || !(voxel_size > 0.0f)) return MSDF_ERR_ARG;
+  if (!fits_int32(n) || !(voxel_size > 0.0f)) return MSDF_ERR_ARG;
   if (n == 0) return MSDF_OK;
   if (!points || !min_bound || !keys) return MSDF_ERR_ARG;
-  voxel_keys_k<<<(unsigned)((n + NN_THREADS - 1) / NN_THREADS), NN_THREADS, 0, (hipStream_t)stream>>>(
-      points, n, min_bound, voxel_size, keys);
+  voxel_keys_k<<<blocks_for(n, NN_THREADS), NN_THREADS, 0, (hipStream_t)stream>>>(points, n, min_bound, voxel_size,
+                                                                                   keys);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_voxel_mean(const float* points, const int64_t* order, const int64_t* seg_start, int64_t n,
                                int64_t m, float* out, void* stream) {
-  if (n < 0 || n > NN_MAX_POINTS || m < 0 || m > n) return MSDF_ERR_ARG;
+  if (!fits_int32(n) || m < 0 || m > n) return MSDF_ERR_ARG;
   if (m == 0) return MSDF_OK;
   if (!points || !order || !seg_start || !out) return MSDF_ERR_ARG;
-  voxel_mean_k<<<(unsigned)((m + NN_THREADS - 1) / NN_THREADS), NN_THREADS, 0, (hipStream_t)stream>>>(
-      points, order, seg_start, n, m, out);
+  voxel_mean_k<<<blocks_for(m, NN_THREADS), NN_THREADS, 0, (hipStream_t)stream>>>(points, order, seg_start, n, m, out);
   return msdf_check_launch();
 }

@@ -24,7 +24,7 @@
 // the normal may be reduced in any order; the minimum over the edges is taken with the edge index as tie-break.
 //
 // Built with -ffp-contract=off: a * x is rounded before the first fma, as the header says.
-#include "common.h"
+#include "tool_common.h"
 #include "../../include/monosdf_obb.h"
 
 namespace {
@@ -36,12 +36,10 @@ constexpr int OBB_SLICE = OBB_THREADS * OBB_PPL;        // points per workgroup
 constexpr int OBB_TILE = 128;                           // planes per workgroup, in LDS (4 KiB)
 constexpr int OBB_GROUP = 4;                            // planes reduced side by side
 constexpr int64_t OBB_MAX_TILES = 65535;                // grid.y
-constexpr int64_t OBB_MAX = 0x7fffffffll;               // sizes and indices are below 2^31
 constexpr double OBB_SIL_EPS = 1e-12;                   // |n . n_face| up to this counts as zero
 constexpr double OBB_DIR_EPS = 1e-24;                   // an edge whose projection keeps less of |d|^2 has no direction
 
-inline bool obb_size_ok(int64_t n) { return n >= 0 && n < OBB_MAX; }
-inline int64_t obb_slices(int64_t n) { return (n + OBB_SLICE - 1) / OBB_SLICE; }
+inline int64_t obb_slices(int64_t n) { return blocks_for(n, OBB_SLICE); }
 
 __device__ __forceinline__ double obb_dot(double px, double py, double pz, double ax, double ay, double az) {
   return fma(pz, az, fma(py, ay, px * ax));
@@ -236,35 +234,33 @@ obb_candidates_k(const double* __restrict__ verts, int h, const double* __restri
 }  // namespace
 
 extern "C" int64_t msdf_obb_support_workspace_bytes(int64_t n_points, int64_t n_planes) {
-  if (!obb_size_ok(n_points) || !obb_size_ok(n_planes)) return -1;
-  const int64_t b = obb_slices(n_points) * n_planes * 12;              // < 2^20 * 2^31 * 12
-  return b > 256 ? b : 256;
+  if (!below_int32_max(n_points) || !below_int32_max(n_planes)) return -1;
+  return workspace_floor(obb_slices(n_points) * n_planes * 12);        // < 2^20 * 2^31 * 12
 }
 
 extern "C" int msdf_obb_support(const float* points, int64_t n_points, const double* planes, int64_t n_planes,
                                 void* workspace, double* value, int32_t* index, void* stream) {
-  if (!obb_size_ok(n_points) || !obb_size_ok(n_planes)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n_points) || !below_int32_max(n_planes)) return MSDF_ERR_ARG;
   if (n_planes == 0) return MSDF_OK;
   if (n_points == 0 || !points || !planes || !workspace || !value || !index) return MSDF_ERR_ARG;
   const int64_t n_slices = obb_slices(n_points);
   double* pval = (double*)workspace;
   int32_t* pidx = (int32_t*)(pval + (size_t)n_slices * (size_t)n_planes);
   const hipStream_t s = (hipStream_t)stream;
-  const int64_t n_tiles = (n_planes + OBB_TILE - 1) / OBB_TILE;
+  const int64_t n_tiles = blocks_for(n_planes, OBB_TILE);
   for (int64_t tile0 = 0; tile0 < n_tiles; tile0 += OBB_MAX_TILES) {
     const int64_t tiles = n_tiles - tile0 < OBB_MAX_TILES ? n_tiles - tile0 : OBB_MAX_TILES;
     obb_support_k<<<dim3((unsigned)n_slices, (unsigned)tiles), OBB_THREADS, 0, s>>>(points, n_points, planes, n_planes,
                                                                                      tile0, pval, pidx);
   }
-  obb_finish_k<<<(unsigned)((n_planes + OBB_THREADS - 1) / OBB_THREADS), OBB_THREADS, 0, s>>>(
-      pval, pidx, n_planes, n_slices, value, index);
+  obb_finish_k<<<blocks_for(n_planes, OBB_THREADS), OBB_THREADS, 0, s>>>(pval, pidx, n_planes, n_slices, value, index);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_obb_candidates(const double* vertices, int64_t n_vertices, const double* normals,
                                    int64_t n_normals, const int32_t* edges, const double* edge_normals,
                                    int64_t n_edges, double* volume, int32_t* edge, double* extents, void* stream) {
-  if (!obb_size_ok(n_vertices) || !obb_size_ok(n_normals) || !obb_size_ok(n_edges)) return MSDF_ERR_ARG;
+  if (!below_int32_max(n_vertices) || !below_int32_max(n_normals) || !below_int32_max(n_edges)) return MSDF_ERR_ARG;
   if (n_normals == 0) return MSDF_OK;
   if (n_vertices == 0 || !vertices || !normals || !volume || !edge || !extents) return MSDF_ERR_ARG;
   if (n_edges > 0 && (!edges || !edge_normals)) return MSDF_ERR_ARG;

@@ -17,14 +17,13 @@
 // TSDF integration (tsdf_integrate_k): one lane owns one voxel of a dense block and loops over the views in the order
 // given; the camera rows are wave-uniform reads, the running mean stays in registers and each voxel is written once.
 // Face rule (tsdf_face_keep_k) and frustum culling (cull_vertices_k): one lane per face / vertex.
-#include "common.h"
+#include "tool_common.h"
 #include "raster_core.h"
 
 namespace {
 
 constexpr int RF_THREADS = 256;
 constexpr unsigned RASTER_INF = 0x7f800000u;       // bits of +inf
-constexpr int64_t RF_MAX = 0x7fffffffll;
 
 // the action of the depth image at an accepted pixel: the minimum of the bits of z
 struct DepthMin {
@@ -83,10 +82,10 @@ tsdf_integrate_k(const float* __restrict__ depth, const float* __restrict__ w2c,
   }
   for (int v = 0; v < p.n_views; ++v) {
     const float* __restrict__ m = w2c + 12 * (size_t)v;                 // the same address in every lane
-    const float pz = m[8] * x + m[9] * y + m[10] * z + m[11];
+    const float pz = affine_row<2>(m, x, y, z);
     if (!(pz > 0.0f)) continue;
-    const float px = m[0] * x + m[1] * y + m[2] * z + m[3];
-    const float py = m[4] * x + m[5] * y + m[6] * z + m[7];
+    const float px = affine_row<0>(m, x, y, z);
+    const float py = affine_row<1>(m, x, y, z);
     const float uf = p.fx * px / pz + p.cx + 0.5f;
     const float vf = p.fy * py / pz + p.cy + 0.5f;
     if (!(uf >= 0.0f && uf < (float)p.width && vf >= 0.0f && vf < (float)p.height)) continue;   // NaN fails
@@ -171,19 +170,13 @@ cull_vertices_k(const float* __restrict__ verts, int64_t V, const float* __restr
   seen[i] = s;
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + RF_THREADS - 1) / RF_THREADS); }
-
-bool intrinsics_ok(float fx, float fy, float cx, float cy) {
-  return fx > 0.0f && fy > 0.0f && cx == cx && cy == cy && fx < __builtin_inff() && fy < __builtin_inff();
-}
-
 }  // namespace
 
 extern "C" int msdf_raster_depth(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                                  const float* w2c, int n_views, float fx, float fy, float cx, float cy, int height,
                                  int width, float znear, float zfar, float pixel_center, float* depth, void* stream) {
-  if (n_verts < 0 || n_verts > RF_MAX || n_faces < 0 || n_faces > RF_MAX || n_views < 0 || n_views > 65535 ||
-      height < 1 || width < 1 || (int64_t)height * width > RF_MAX || !intrinsics_ok(fx, fy, cx, cy) ||
+  if (!fits_int32(n_verts) || !fits_int32(n_faces) || n_views < 0 || n_views > 65535 ||
+      height < 1 || width < 1 || (int64_t)height * width > MSDF_COUNT_MAX || !intrinsics_ok(fx, fy, cx, cy) ||
       !(znear > 0.0f) || !(zfar >= znear) || !(pixel_center == pixel_center))
     return MSDF_ERR_ARG;
   if (n_views == 0) return MSDF_OK;
@@ -191,13 +184,13 @@ extern "C" int msdf_raster_depth(const float* verts, int64_t n_verts, const int3
   const hipStream_t s = (hipStream_t)stream;
   const int64_t n_px = (int64_t)n_views * height * width;
   unsigned* img = (unsigned*)depth;
-  raster_clear_k<<<blocks_for(n_px), RF_THREADS, 0, s>>>(img, n_px);
+  raster_clear_k<<<blocks_for(n_px, RF_THREADS), RF_THREADS, 0, s>>>(img, n_px);
   if (n_faces > 0 && n_verts > 0) {
     const RasterCam cam{fx, fy, cx, cy, pixel_center, znear, zfar, height, width};
-    raster_tri_k<<<dim3(blocks_for(n_faces), (unsigned)n_views), RF_THREADS, 0, s>>>(verts, n_verts, faces, n_faces,
-                                                                                     w2c, cam, img);
+    raster_tri_k<<<dim3((unsigned)blocks_for(n_faces, RF_THREADS), (unsigned)n_views), RF_THREADS, 0, s>>>(
+        verts, n_verts, faces, n_faces, w2c, cam, img);
   }
-  raster_finish_k<<<blocks_for(n_px), RF_THREADS, 0, s>>>(img, n_px);
+  raster_finish_k<<<blocks_for(n_px, RF_THREADS), RF_THREADS, 0, s>>>(img, n_px);
   return msdf_check_launch();
 }
 
@@ -205,39 +198,40 @@ extern "C" int msdf_tsdf_integrate(const float* depth, const float* w2c, int n_v
                                    float cy, int height, int width, float ox, float oy, float oz, int i0, int j0, int k0, int nx, int ny,
                                    int nz, float voxel_length, float sdf_trunc, float depth_trunc, int resume,
                                    float* tsdf, float* weight, void* stream) {
-  if (n_views < 0 || height < 1 || width < 1 || (int64_t)height * width > RF_MAX || nx < 1 || ny < 1 || nz < 1 ||
-      (int64_t)nx * ny * nz > RF_MAX || i0 < 0 || j0 < 0 || k0 < 0 || (int64_t)i0 + nx > (1 << 24) ||
+  if (n_views < 0 || height < 1 || width < 1 || (int64_t)height * width > MSDF_COUNT_MAX || nx < 1 || ny < 1 ||
+      nz < 1 || (int64_t)nx * ny * nz > MSDF_COUNT_MAX || i0 < 0 || j0 < 0 || k0 < 0 || (int64_t)i0 + nx > (1 << 24) ||
       (int64_t)j0 + ny > (1 << 24) || (int64_t)k0 + nz > (1 << 24) || !intrinsics_ok(fx, fy, cx, cy) ||
       !(voxel_length > 0.0f) || !(sdf_trunc > 0.0f) || !(depth_trunc == depth_trunc) || !(ox - ox == 0.0f) || !(oy - oy == 0.0f) || !(oz - oz == 0.0f) || !tsdf || !weight ||
       (n_views > 0 && (!depth || !w2c)))
     return MSDF_ERR_ARG;
   const TsdfArgs p{fx, fy, cx, cy, ox, oy, oz, voxel_length, sdf_trunc, depth_trunc,
                    height, width, nx, ny, nz, n_views, i0, j0, k0, resume ? 1 : 0};
-  tsdf_integrate_k<<<blocks_for((int64_t)nx * ny * nz), RF_THREADS, 0, (hipStream_t)stream>>>(depth, w2c, p, tsdf,
-                                                                                             weight);
+  tsdf_integrate_k<<<blocks_for((int64_t)nx * ny * nz, RF_THREADS), RF_THREADS, 0, (hipStream_t)stream>>>(
+      depth, w2c, p, tsdf, weight);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_tsdf_face_keep(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                                    const float* weight, int nx, int ny, int nz, uint8_t* keep, void* stream) {
-  if (n_verts < 0 || n_verts > RF_MAX || n_faces < 0 || n_faces > RF_MAX || nx < 1 || ny < 1 || nz < 1 ||
-      (int64_t)nx * ny * nz > RF_MAX)
+  if (!fits_int32(n_verts) || !fits_int32(n_faces) || nx < 1 || ny < 1 || nz < 1 ||
+      (int64_t)nx * ny * nz > MSDF_COUNT_MAX)
     return MSDF_ERR_ARG;
   if (n_faces == 0) return MSDF_OK;
   if (!verts || !faces || !weight || !keep) return MSDF_ERR_ARG;
-  tsdf_face_keep_k<<<blocks_for(n_faces), RF_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces, n_faces,
-                                                                               weight, nx, ny, nz, keep);
+  tsdf_face_keep_k<<<blocks_for(n_faces, RF_THREADS), RF_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, faces,
+                                                                                            n_faces, weight, nx, ny, nz,
+                                                                                            keep);
   return msdf_check_launch();
 }
 
 extern "C" int msdf_cull_vertices(const float* verts, int64_t n_verts, const float* w2c, int n_views, float fx,
                                   float fy, float cx, float cy, int height, int width, uint8_t* seen, void* stream) {
-  if (n_verts < 0 || n_verts > RF_MAX || n_views < 0 || height < 1 || width < 1 || !intrinsics_ok(fx, fy, cx, cy))
+  if (!fits_int32(n_verts) || n_views < 0 || height < 1 || width < 1 || !intrinsics_ok(fx, fy, cx, cy))
     return MSDF_ERR_ARG;
   if (n_verts == 0) return MSDF_OK;
   if (!verts || !seen || (n_views > 0 && !w2c)) return MSDF_ERR_ARG;
-  cull_vertices_k<<<blocks_for(n_verts), RF_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, w2c, n_views, fx, fy,
-                                                                              cx, cy, (float)width, (float)height,
-                                                                              seen);
+  cull_vertices_k<<<blocks_for(n_verts, RF_THREADS), RF_THREADS, 0, (hipStream_t)stream>>>(verts, n_verts, w2c, n_views,
+                                                                                           fx, fy, cx, cy, (float)width,
+                                                                                           (float)height, seen);
   return msdf_check_launch();
 }

@@ -1,5 +1,5 @@
 """Mesh rendering on the GPU: which face every pixel shows, shaded frames and the depth L1 of two meshes
-(csrc/meshrender.hip, ABI include/mesh/monosdf_render.h, which states every rule operation by operation).
+(csrc/meshrender.hip, ABI include/monosdf_render.h, which states every rule operation by operation).
 
 * ``visibility``: depth and face index per pixel from every pose, with back- or front-face culling; with
   ``cull='none'`` the depth is bit for bit ``mesh_refuse.render_depth``'s (one rasteriser, csrc/raster_core.h).
@@ -199,7 +199,7 @@ def shade(face, depth, vertices, faces, poses, K, normals=None, options=RenderOp
     point lights at centre + extent (p.x right + p.y up + p.z toward the viewer) of the mesh's bounding box, in the
     camera's axes: the rig moves with the camera.  colour = base (ambient + sum kd cos_theta c) + sum ks cos_alpha^s c,
     clamped to [0, 1]; ``base_color`` is one colour, ``vertex_colors`` [V, 3] float32 are interpolated instead.
-    Background pixels get ``options.background_color`` exactly.  include/mesh/monosdf_render.h states every operation."""
+    Background pixels get ``options.background_color`` exactly.  include/monosdf_render.h states every operation."""
     name = 'shade'
     ma.check_tensor(name, 'face', face, (torch.int32,), '[n, H, W]')
     ma.check_tensor(name, 'depth', depth, shape='[n, H, W]')

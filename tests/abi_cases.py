@@ -9,12 +9,15 @@ INCLUDE = os.path.join(ROOT, 'include')
 VERSIONED = 'monosdf_hip.h'
 
 # The additive headers: the prefix of their names, their source file, whether that file is built with
-# -ffp-contract=off, and their entry points.  The versioned header has no list of names here: its count is stated
-# below, and the features that extended it keep their own subsets (test_dtu_cpu, test_refuse_cpu, test_mesh_eval_cpu).
+# -ffp-contract=off, and their entry points; where it applies, `named_in`: the other headers whose text may name these
+# entry points, and `depends`: further headers under csrc/ that the source shares with other sources.  The versioned
+# header has no list of names here: its count is stated below, and the features that extended it keep their own
+# subsets (test_dtu_cpu, test_refuse_cpu, test_mesh_eval_cpu).
 VERSIONED_COUNT = 64
 ADDITIVE = {
-    'monosdf_gridnn.h': dict(prefix='msdf_gnn_', source='gridnn', no_contraction=True, entries=(
-        'msdf_gnn_workspace_bytes', 'msdf_gnn_cells', 'msdf_gnn_records', 'msdf_gnn_query')),
+    'monosdf_gridnn.h': dict(prefix='msdf_gnn_', source='gridnn', no_contraction=True, named_in=('monosdf_icp.h',),
+                             entries=('msdf_gnn_workspace_bytes', 'msdf_gnn_cells', 'msdf_gnn_records',
+                                      'msdf_gnn_query')),
     'monosdf_meshcc.h': dict(prefix='msdf_mcc_', source='meshcc', no_contraction=False, entries=(
         'msdf_mcc_edge_keys', 'msdf_mcc_init', 'msdf_mcc_link_edges', 'msdf_mcc_link_vertices', 'msdf_mcc_flatten',
         'msdf_mcc_segment_sum')),
@@ -25,6 +28,10 @@ ADDITIVE = {
     'monosdf_icp.h': dict(prefix='msdf_icp_', source='icp', no_contraction=True, entries=(
         'msdf_icp_state_bytes', 'msdf_icp_workspace_bytes', 'msdf_icp_transform', 'msdf_icp_accumulate',
         'msdf_icp_solve')),
+    'monosdf_render.h': dict(prefix='msdf_rnd_', source='meshrender', no_contraction=True, depends=('raster_core.h',),
+                             entries=('msdf_rnd_visibility_workspace_bytes', 'msdf_rnd_visibility',
+                                      'msdf_rnd_vertex_normals', 'msdf_rnd_shade', 'msdf_rnd_depth_l1',
+                                      'msdf_rnd_views_see')),
 }
 
 C_SCALARS = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'uint32_t': ctypes.c_uint32, 'int64_t': ctypes.c_int64,

@@ -132,7 +132,7 @@ def _rot(m, p):
 def phong(dtype, face, depth, rows, K, vertices, faces, normals, table, centre, extent, base=(1.0, 1.0, 1.0),
           colors=None, flat=False, two_sided=False, pixel_center=0.5, mutant_unnormalised=False,
           mutant_world_lights=False, mutant_unclamped_specular=False):
-    """The shading rule of include/mesh/monosdf_render.h in ``dtype`` (np.float64: the reference; np.float32: a copy
+    """The shading rule of include/monosdf_render.h in ``dtype`` (np.float64: the reference; np.float32: a copy
     whose distance from the reference measures what fp32 costs on a scene).  face, depth: [n,H,W] (depth fp32 as the
     renderer wrote it); rows: [n,3,4] fp32 world-to-camera; table: the 42 floats of ``RenderOptions.light_table``.
     -> rgb [n,H,W,3] ``dtype``."""

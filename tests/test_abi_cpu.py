@@ -11,7 +11,14 @@ import abi_cases as abi
 from monosdf_amd import _lib
 
 HEADERS = _lib.headers()
-MAKEFILE = open(os.path.join(abi.ROOT, 'monosdf_amd', 'csrc', 'Makefile')).read()
+CSRC = os.path.join(abi.ROOT, 'monosdf_amd', 'csrc')
+MAKEFILE = open(os.path.join(CSRC, 'Makefile')).read()
+
+
+def prerequisites(obj):
+    """What the Makefile's dependency lines (`targets: prerequisites`, no variable assignment) give the object."""
+    lines = [re.match(r'^([\w.% ]+): (?!EXTRA)(.*)$', l) for l in MAKEFILE.splitlines()]
+    return {word for m in lines if m and obj in m.group(1).split() for word in m.group(2).split()}
 
 
 def test_every_header_with_entry_points_has_a_table():
@@ -48,6 +55,7 @@ def test_header_and_table_agree(header):
         assert len(table[name]) == len(accepted), (name, len(table[name]), len(accepted))
         for i, (have, want) in enumerate(zip(table[name], accepted)):
             assert have in want, (name, i, have, want)
+            assert header == abi.VERSIONED or len(want) == 1, (name, i, want)    # additive headers pass no struct
             if have is ctypes.c_void_p and len(want) == 2:
                 tables.add(name)
         assert (ret == 'int64_t') == name.endswith('_bytes'), name
@@ -70,8 +78,10 @@ def test_loaded_library_is_bound_as_the_header_says(header):
 @pytest.mark.parametrize('header', sorted(abi.ADDITIVE))
 def test_additive_header_keeps_to_itself(header):
     """An additive header's names carry its prefix and end in a stream unless they size a workspace; no other table
-    and no other header's text holds them; its source is built, depends on the header, and is compiled without
-    contraction where its arithmetic is pinned operation by operation."""
+    holds them and no other header's text names them, but for the headers the case lists; it leaves the ABI version to
+    the versioned header; its source is built, depends on the header, and is compiled without contraction where its
+    arithmetic is pinned operation by operation; a further header its source shares with other sources is a
+    prerequisite of every object whose source includes it."""
     case = abi.ADDITIVE[header]
     prefix, source = case['prefix'], case['source']
     for ret, name, params in abi.prototypes(header):
@@ -82,12 +92,19 @@ def test_additive_header_keeps_to_itself(header):
             assert not [n for n in _lib.signatures(other) if n.startswith(prefix)], other
             declared = [p[1] for p in abi.prototypes(other)]
             assert not [n for n in declared if n.startswith(prefix)], other
-    assert prefix not in abi.header_text(abi.VERSIONED)
+            assert prefix not in abi.header_text(other) or other in case.get('named_in', ()), other
+    assert 'MSDF_ABI_VERSION' not in abi.header_text(header).replace('MSDF_ABI_VERSION are unchanged', '')
     srcs = [l for l in MAKEFILE.splitlines() if l.startswith('SRCS =')]
     assert len(srcs) == 1 and source + '.hip' in srcs[0].split()
     assert re.search(r'^%s\.o: .*include/%s' % (source, re.escape(header)), MAKEFILE, flags=re.M)
     contraction_off = re.search(r'^%s\.o: EXTRA \+= .*-ffp-contract=off' % source, MAKEFILE, flags=re.M)
     assert bool(contraction_off) == case['no_contraction']
+    for shared in case.get('depends', ()):
+        users = [s[:-4] for s in srcs[0].split()
+                 if s.endswith('.hip') and '#include "%s"' % shared in open(os.path.join(CSRC, s)).read()]
+        assert source in users and len(users) > 1, (shared, users)
+        for user in users:
+            assert shared in prerequisites(user + '.o'), (shared, user)
 
 
 def test_icp_header_leaves_the_grid_header_alone():

@@ -1,12 +1,11 @@
-"""CPU tests of the mesh renderer: the tool header include/mesh/monosdf_render.h against its table in
-monosdf_amd/_lib.py by the rules the additive headers obey (tests/abi_cases.py), the Makefile, the host refusals of
-every entry point and of utils/mesh_render.py, the readers, and certificates for the scenes of the GPU tests
+"""CPU tests of the mesh renderer (its header include/monosdf_render.h is held against its table and the Makefile by
+tests/test_abi_cpu.py, as every additive header is): the host refusals of every entry point and of
+utils/mesh_render.py, the readers, and certificates for the scenes of the GPU tests
 (tests/test_gpu_meshrender.py): few exempt pixels, both facings present, and every mutant of the restatements
 (tests/render_numpy.py) visible on them."""
 import ctypes
 import functools
 import os
-import re
 import subprocess
 import sys
 
@@ -14,7 +13,6 @@ import numpy as np
 import pytest
 import torch
 
-import abi_cases as abi
 import refuse_numpy as rfn
 import render_numpy as rn
 
@@ -24,73 +22,15 @@ sys.path.insert(0, ROOT)
 from monosdf_amd import _lib                                    # noqa: E402
 from monosdf_amd.utils import mesh_render as mrd                # noqa: E402
 
-HEADER = 'mesh/monosdf_render.h'
-PREFIX = 'msdf_rnd_'
-ENTRIES = ('msdf_rnd_visibility_workspace_bytes', 'msdf_rnd_visibility', 'msdf_rnd_vertex_normals', 'msdf_rnd_shade',
-           'msdf_rnd_depth_l1', 'msdf_rnd_views_see')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'render')
-MAKEFILE = open(os.path.join(ROOT, 'monosdf_amd', 'csrc', 'Makefile')).read()
 K = (50.0, 50.0, 32.0, 24.0)
 H, W = 48, 64
-
-
-# ---- the tool header
-
-
-def test_tool_header_has_a_table_of_its_own():
-    assert _lib.tool_headers() == [HEADER] and HEADER not in _lib.headers()
-    assert sorted(_lib.tool_signatures(HEADER)) == sorted(ENTRIES)
-    assert '#define MSDF_ABI_VERSION 8' in abi.header_text(abi.VERSIONED) and _lib.ABI_VERSION == 8
-    assert 'MSDF_ABI_VERSION' not in abi.header_text(HEADER).replace('MSDF_ABI_VERSION are unchanged', '')
-
-
-def test_tool_header_and_table_agree():
-    assert ctypes.c_int is ctypes.c_int32
-    protos, table = abi.prototypes(HEADER), _lib.tool_signatures(HEADER)
-    assert sorted(p[1] for p in protos) == sorted(table) and len(protos) == len(table)
-    for ret, name, params in protos:
-        accepted = abi.accepted_argtypes(name, params)
-        assert len(table[name]) == len(accepted), (name, len(table[name]), len(accepted))
-        for i, (have, want) in enumerate(zip(table[name], accepted)):
-            assert have in want and len(want) == 1, (name, i, have, want)
-        assert (ret == 'int64_t') == name.endswith('_bytes'), name
-
-
-def test_tool_header_keeps_to_itself():
-    for ret, name, params in abi.prototypes(HEADER):
-        assert name.startswith(PREFIX), name
-        assert (abi.parameters(params)[-1][-1] == 'stream') != name.endswith('_bytes'), name
-    for other in _lib.headers():
-        assert not [n for n in _lib.signatures(other) if n.startswith(PREFIX)], other
-        assert not [p[1] for p in abi.prototypes(other) if p[1].startswith(PREFIX)], other
-        assert PREFIX not in abi.header_text(other), other
-    srcs = [l for l in MAKEFILE.splitlines() if l.startswith('SRCS =')]
-    assert len(srcs) == 1 and 'meshrender.hip' in srcs[0].split()
-    assert re.search(r'^meshrender\.o: EXTRA \+= .*-ffp-contract=off', MAKEFILE, flags=re.M)
-    dep = re.search(r'^meshrender\.o: (.*include/mesh/monosdf_render\.h.*)$', MAKEFILE, flags=re.M)
-    assert dep and 'raster_core.h' in dep.group(1).split()
-    assert re.search(r'^refuse\.o: .*raster_core\.h', MAKEFILE, flags=re.M)
-
-
-def test_an_entry_in_both_tables_is_refused_at_import():
-    source = open(_lib.__file__).read()
-    twice = source.replace("}, 'monosdf_meshcc.h': {", "    'msdf_rnd_shade': [],\n}, 'monosdf_meshcc.h': {", 1)
-    assert twice != source
-    with pytest.raises(ImportError, match='two headers.*msdf_rnd_shade'):
-        exec(compile(twice, _lib.__file__, 'exec'), {'__name__': 'abi_twice', '__file__': _lib.__file__})
 
 
 def _lib_or_skip():
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip('library not built (run python __graft_entry__.py)')
     return _lib.load()
-
-
-def test_loaded_library_binds_the_tool_header():
-    lib = _lib_or_skip()
-    for ret, name, _ in abi.prototypes(HEADER):
-        assert getattr(lib, name).restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert getattr(lib, name).argtypes == _lib.tool_signatures(HEADER)[name], name
 
 
 BIG = 2 ** 31
