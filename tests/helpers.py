@@ -1,4 +1,6 @@
-"""Shared helpers for the parity tests (load a golden case, rebuild its inputs)."""
+"""Shared helpers for the parity tests (load a golden case, rebuild its inputs, the error measure and its bars).  What a
+test does with a whole MonoSDFNetwork -- build it, make the oracle's state, run a pass, compare parameter gradients or
+whole training steps -- is in the harness next to this file, tests/harness.py."""
 import ast
 import os
 

@@ -23,7 +23,9 @@ def _worker(rank, world, port, q):
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         import sys
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from harness import oracle_state
         from monosdf_amd import parallel
         from oracle import config, monosdf_oracle as mo, synth
         torch.set_num_threads(2)
@@ -38,7 +40,7 @@ def _worker(rank, world, port, q):
         rows = torch.cat([out['rgb_values'], out['depth_values'], out['normal_map']], 1)
         full = parallel.all_gather_rows(rows.detach())
         # gradient averaging: loss over the local rays, mean over ranks == weighted single-process result
-        st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+        st = oracle_state(state, grad=True)
         o2 = mo.render(st, conf, mine, torch.arange(lo, hi), True, False, None)
         o2['rgb_values'].sum().backward()
         params = [torch.nn.Parameter(v.detach().clone()) for v in st.values() if v.grad is not None]
@@ -48,7 +50,7 @@ def _worker(rank, world, port, q):
         if rank == 0:
             ref = mo.render(state, conf, rays, torch.arange(n), True, False, None)
             ref_rows = torch.cat([ref['rgb_values'], ref['depth_values'], ref['normal_map']], 1)
-            st1 = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+            st1 = oracle_state(state, grad=True)
             r1 = mo.render(st1, conf, rays, torch.arange(n), True, False, None)
             r1['rgb_values'].sum().backward()
             g_single = [v.grad / world for v in st1.values() if v.grad is not None]

@@ -14,42 +14,15 @@ import functools
 import pytest
 import torch
 
-from oracle import config, synth
+from harness import assert_same_step, run_pass, shared_weights, step_record, switched, to_device
+from reuse_cases import N_EXTRA, OUT_KEYS, inputs as _inputs, model as _model
 
 pytestmark = pytest.mark.gpu
 
-NETS = {'w64_skip': 64, 'w256_skip': 256}
+NETS = ('w256_skip', 'w64_skip')
 RAYS = (2, 3, 6)
-CASES = [(net, n) for net in sorted(NETS) for n in RAYS]
-N_EVAL, N_EXTRA = 128, 32
-OUT_KEYS = ('rgb', 'rgb_values', 'depth_values', 'z_vals', 'depth_vals', 'sdf', 'weights', 'grad_theta',
-            'grad_theta_nei', 'normal_map')
+CASES = [(net, n) for net in NETS for n in RAYS]
 WS_BLOCKS = (('H', 'PM'), ('PM', 'IN0'), ('IN0', 'QB'))       # a block of the workspace and the one behind it
-
-
-@functools.lru_cache(maxsize=None)
-def _conf_state(net, beta):
-    conf = config.mlp_config(NETS[net], 8, beta=beta)
-    return conf, synth.make_state(conf, seed=5, jitter=0.3)
-
-
-def _model(net, beta):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
-    conf, state = _conf_state(net, beta)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    return m.cuda().train()
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(net, n, beta, table):
-    conf, _ = _conf_state(net, beta)
-    # sharp state (`table`): ray seeds at which the oracle's sampler needs exactly two rounds for every (net, n) here,
-    # with the first round's largest beta 1.8 to 4 times the target -- no marginal decision
-    rays = synth.make_rays(n, seed=(50 if table else 3) + n, random_pose=True)
-    noise = synth.make_noise_table(conf, n, seed=7) if table else synth.make_noise(conf, n, N_EVAL, seed=7)
-    return rays, noise
 
 
 class _Recorder:
@@ -84,37 +57,25 @@ def _step(net, n, reuse_last, beta=0.1, table=False):
     rays, noise = _inputs(net, n, beta, table)
     m = _model(net, beta)
     m.speculate_rounds = True
-    m._noise = {k: v.cuda() for k, v in noise.items()}
     sdfnet = m.implicit_network
     made, make = [], sdfnet.sdf_reuse
     sdfnet.sdf_reuse = lambda *a, **k: made.append(make(*a, **k)) or made[-1]
-    was, ops.FG_REUSE_LAST = ops.FG_REUSE_LAST, reuse_last
-    try:
-        with _Recorder() as rec:
-            out = m({k: v.cuda() for k, v in rays.items()}, torch.arange(n).cuda(), if_pixel_input=True)
-            loss = mo.probe_loss(out)
-            loss.backward()
-    finally:
-        ops.FG_REUSE_LAST = was
+    with switched(ops, 'FG_REUSE_LAST', reuse_last), _Recorder() as rec:
+        out = run_pass(m, rays, torch.arange(n), noise)
+        loss = mo.probe_loss(out)
+        loss.backward()
     torch.cuda.synchronize()
     reuse = made[-1]                    # the pass that was kept
     woff, _ = planlib.sdf_workspace(reuse.mlp.mp, reuse.P_pad)
-    return {'out': {k: out[k].detach().clone() for k in OUT_KEYS}, 'loss': loss.detach().clone(),
-            'grads': {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None},
-            'ws': {k: reuse.ws[woff[k]:woff[nxt]].clone() for k, nxt in WS_BLOCKS},
-            'rounds': m.ray_sampler.last_rounds, 'repeats': m.ray_sampler.stats['repeats'],
-            'wg_first': [a.wg_first for a in rec.fg], 'n_reuse': reuse.n_reuse, 'n_wg': reuse.P_pad // 64,
-            'taken': int(reuse.flags[1]) == 0 and int(reuse.h_saved[0]) == 1}
+    return dict(step_record(m, out, loss, OUT_KEYS),
+                ws={k: reuse.ws[woff[k]:woff[nxt]].clone() for k, nxt in WS_BLOCKS},
+                wg_first=[a.wg_first for a in rec.fg], n_reuse=reuse.n_reuse, n_wg=reuse.P_pad // 64,
+                taken=int(reuse.flags[1]) == 0 and int(reuse.h_saved[0]) == 1)
 
 
 def _assert_same_step(a, b):
-    assert sorted(a['out']) == sorted(b['out']) and sorted(a['grads']) == sorted(b['grads'])
-    for k in a['out']:
-        assert torch.equal(a['out'][k], b['out'][k]), k
-    assert torch.equal(a['loss'], b['loss'])
+    assert_same_step(a, b)
     assert len(a['grads']) >= 20
-    for k in a['grads']:
-        assert torch.equal(a['grads'][k], b['grads'][k]), k
     for k in a['ws']:
         assert a['ws'][k].numel() > 0 and torch.equal(a['ws'][k], b['ws'][k]), k
 
@@ -154,14 +115,13 @@ def test_entry_point_with_every_rotation():
     net, n = 'w256_skip', 6
     rays, noise = _inputs(net, n, 0.1, False)
     m = _model(net, 0.1)
-    m._noise = {k: v.cuda() for k, v in noise.items()}
+    m._noise = to_device(noise)
     dev = torch.device('cuda', torch.cuda.current_device())
     sdfnet, smp = m.implicit_network, m.ray_sampler
     S = smp.N_samples + N_EXTRA + 2
     P, n_wg = n * S + 4 * n, (n * S + 4 * n + 63) // 64
     d, o = rays['ray_dirs'].cuda().contiguous(), rays['ray_cam_loc'].cuda().contiguous()
-    sdfnet.share(dev)
-    try:
+    with shared_weights(sdfnet, dev):
         fused = sdfnet.packed(dev)[0]
         beta0 = ops.effective_beta(m.density.beta, m.density.beta_min_f)
         reuse = sdfnet.sdf_reuse(dev, n, S, N_EXTRA, 4 * n, True)
@@ -197,5 +157,3 @@ def test_entry_point_with_every_rotation():
             assert fn(C.byref(fused.plan), C.byref(a), stream) == 1, w          # MSDF_ERR_ARG
         a.wg_first = 1
         assert fn(C.byref(fused.mp.build_b16(2)), C.byref(a), stream) == 3      # MSDF_ERR_UNSUPPORTED
-    finally:
-        sdfnet.unshare()

@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench                                    # noqa: E402  (model_conf / make_rays of the bench workload)
+from harness import assert_same_step, step_record  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 N = bench.N_RAYS
@@ -46,14 +47,9 @@ def test_fullsize_compositing_identities_and_reproducibility(precision):
     depth = (w * z).sum(1, keepdim=True) / (w.sum(1, keepdim=True) + 1e-8) * rays['ray_dirs_tmp'][:, 2:]
     assert (depth - out['depth_values']).abs().max().item() < 2e-5
     assert (out['depth_vals'] - z * rays['ray_dirs_tmp'][:, 2:]).abs().max().item() == 0.0
-    g1 = {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
-    out2, loss2 = _step(model, rays)
-    assert loss.item() == loss2.item()
-    for k in ('rgb_values', 'depth_values', 'normal_map', 'sdf', 'weights', 'grad_theta'):
-        assert torch.equal(out[k], out2[k]), k                 # no float atomics on this path: bitwise reproducible
-    for n, p in model.named_parameters():
-        if p.grad is not None:
-            assert torch.equal(p.grad, g1[n]), n
+    keys = ('rgb_values', 'depth_values', 'normal_map', 'sdf', 'weights', 'grad_theta')
+    first = step_record(model, out, loss, keys)
+    assert_same_step(first, step_record(model, *_step(model, rays), keys))    # no float atomics here: bitwise reproducible
 
 
 def _central_difference(p, d, eps, value_fn):

@@ -31,21 +31,15 @@ def _worker(rank, world, port, q):
     try:
         sys.path.insert(0, HERE)
         sys.path.insert(0, os.path.dirname(HERE))
+        from harness import case_model, run_pass
         from helpers import Case
         from monosdf_amd import parallel
-        from monosdf_amd.conf import ConfigTree
-        from monosdf_amd.model.network import MonoSDFNetwork
         from monosdf_amd.utils import render
         res = {}
 
-        def build(case):
-            m = MonoSDFNetwork(ConfigTree.from_dict(case.conf))
-            m.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
-            return m.cuda().eval()
-
         # 1. strong scaling of one batch: the whole batch needs 5 rounds, its second half alone 3
         c = Case('mlp_w64_eval_k5')
-        m = build(c)
+        m = case_model(c, training=False)
         n = c.inputs['ray_dirs'].shape[0]
         lo, hi = parallel.shard_slice(n)
         mine = {k: v[lo:hi].cuda() for k, v in c.inputs.items()}
@@ -68,14 +62,14 @@ def _worker(rank, world, port, q):
         res['own_history'] = list(m.ray_sampler._hist[0])
         m.ray_sampler.global_rounds = None
         m.speculate_rounds = False
-        full = m({k: v.cuda() for k, v in c.inputs.items()}, c.indices.cuda(), if_pixel_input=True)
+        full = run_pass(m, c.inputs, c.indices)
         res['single'] = torch.cat([full['z_vals'], full['rgb_values'], full['depth_values'], full['normal_map']], 1).cpu()
         res['single_rounds'] = m.ray_sampler.last_rounds
         res['rounds'] = rounds
 
         # 2. sharded image render (configs[3] plumbing on the HIP model): 8 chunks, ragged last one
         ci = Case('mlp_w64_image_eval')
-        mi = build(ci)
+        mi = case_model(ci, training=False)
         total, split = 73, 10
         g = torch.Generator().manual_seed(5)
         inputs = {'uv': (torch.rand(1, total, 2, generator=g) * 384).cuda(), 'pose': ci.inputs['pose'].cuda(),
@@ -98,7 +92,7 @@ def _worker(rank, world, port, q):
         # its own message from the post-accumulate hook (behind the scatter, before the weight-gradient kernels), the
         # MLP block as one flat message; the result is the mean of the two ranks' single-process gradients
         cg = Case('grid_small_train')
-        mg = build(cg).train()
+        mg = case_model(cg, training=True)
         ng = cg.inputs['ray_dirs'].shape[0]
         half = ng // 2
 

@@ -8,20 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+from harness import build_model, case_model, check_param_grads, oracle_state, run_pass, to_device as _cuda
 from helpers import ALL_CASES, Case, check, digest, hash_table_gradients, rel_err
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
-
-
-def _model(case, training=None, precision='fp32'):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
-    m = MonoSDFNetwork(ConfigTree.from_dict(case.conf), if_hdr=case.spec.get('if_hdr', False))
-    m.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
-    m.train(case.training if training is None else training)
-    return m.cuda().set_precision(precision)
 
 
 # the matrix cores of the fused MLP kernels: fp32 and bf16x6 (fp32-grade products from three bf16 planes) are held to
@@ -32,22 +24,14 @@ def precision(request):
     return request.param
 
 
-def _cuda(d):
-    return {k: v.cuda() for k, v in d.items()}
-
-
-def _oracle_state(case, grad=False):
-    return {k: v.clone().requires_grad_(grad and v.dtype.is_floating_point) for k, v in case.state.items()}
-
-
 @pytest.mark.parametrize('name', ['mlp_w64_eval', 'mlp_w256_eval', 'gridless_w128_train'])
 def test_sdf_network_stages(name, precision, errlog):
     from oracle import monosdf_oracle as mo
     c = Case(name)
-    m = _model(c, training=False, precision=precision)
+    m = case_model(c, training=False, precision=precision)
     g = torch.Generator().manual_seed(3)
     x = (torch.rand(1000 + 37, 3, generator=g) * 2 - 1) * 1.3       # some points outside the sphere (clamp)
-    st = _oracle_state(c)
+    st = oracle_state(c.state)
     sdf_o, feat_o, grad_o = mo.get_outputs(st, c.conf, x, create_graph=False)
     sdf, feat, grad = m.implicit_network.get_outputs(x.cuda())
     test = 'sdf_stages.' + precision
@@ -66,13 +50,13 @@ def test_sdf_network_double_backward(name, precision, errlog):
     """d/d params of  <a, sdf> + <B, feat> + <C, grad sdf>  (second order through grad sdf)."""
     from oracle import monosdf_oracle as mo
     c = Case(name)
-    m = _model(c, training=True, precision=precision)
+    m = case_model(c, training=True, precision=precision)
     g = torch.Generator().manual_seed(5)
     P = 777
     x = (torch.rand(P, 3, generator=g) * 2 - 1) * 1.2
     F = c.conf['feature_vector_size']
     ca, cb, cc = torch.randn(P, 1, generator=g), torch.randn(P, F, generator=g) * 0.1, torch.randn(P, 3, generator=g)
-    st = _oracle_state(c, grad=True)
+    st = oracle_state(c.state, grad=True)
     sdf_o, feat_o, grad_o = mo.get_outputs(st, c.conf, x)
     loss_o = (ca * sdf_o).sum() + (cb * feat_o).sum() + (cc * grad_o).sum()
     names = [n for n in st if n.startswith('implicit_network.lin')]
@@ -83,18 +67,15 @@ def test_sdf_network_double_backward(name, precision, errlog):
     scale = ((ca * sdf_o).abs().sum() + (cb * feat_o).abs().sum() + (cc * grad_o).abs().sum()).item()
     assert abs(loss.item() - loss_o.item()) < 1e-4 * max(1.0, scale)
     loss.backward()
-    params = dict(m.named_parameters())
     # second-order parameter gradients (the bf16x3 core drops the lo*lo term of every product, 2^-16 relative)
-    for n, go in zip(names, g_o):
-        assert params[n].grad is not None, n
-        check(errlog, 'sdf_double_backward.' + precision, name, n, rel_err(params[n].grad, go))
+    check_param_grads(errlog, 'sdf_double_backward.' + precision, name, m, dict(zip(names, g_o)), names)
 
 
 def test_color_network_forward_backward(precision, errlog):
     from oracle import monosdf_oracle as mo
     for name in ['mlp_w64_eval', 'mlp_w256_eval', 'mlp_w64_code_train']:
         c = Case(name)
-        m = _model(c, training=True, precision=precision)
+        m = case_model(c, training=True, precision=precision)
         g = torch.Generator().manual_seed(7)
         n_rays, S = 12, 9
         P = n_rays * S
@@ -105,7 +86,7 @@ def test_color_network_forward_backward(precision, errlog):
         dirs = torch.nn.functional.normalize(torch.randn(n_rays, 3, generator=g), dim=1)
         idx = torch.arange(n_rays) % 5
         w = torch.randn(P, 3, generator=g)
-        st = _oracle_state(c, grad=True)
+        st = oracle_state(c.state, grad=True)
         nrm_o, feat_o = nrm.clone().requires_grad_(True), feat.clone().requires_grad_(True)
         dirs_pp = dirs.unsqueeze(1).repeat(1, S, 1).reshape(-1, 3)
         rgb_o = mo.color_network(st, c.conf, pts, nrm_o, dirs_pp, feat_o, idx, True)
@@ -117,9 +98,7 @@ def test_color_network_forward_backward(precision, errlog):
         test = 'color_network.' + precision
         check(errlog, test, name, 'rgb', rel_err(rgb, rgb_o))
         (w.cuda() * rgb).sum().backward()
-        params = dict(m.named_parameters())
-        for n, go in zip(names, g_o):
-            check(errlog, test, name, n, rel_err(params[n].grad, go))
+        check_param_grads(errlog, test, name, m, dict(zip(names, g_o)), names)
         check(errlog, test, name, 'd/d normals', rel_err(nrm_g.grad, g_o[-2]))
         check(errlog, test, name, 'd/d features', rel_err(feat_g.grad, g_o[-1]))
 
@@ -470,7 +449,7 @@ def test_sampler_against_golden(name, errlog):
     """get_z_vals alone against the reference's z_vals: 1 to 5 rounds, converged and not (every exit of the
     loop, ray_sampler.py:125,179-207).  z is compared as a fraction of the sampler's far bound (3.85)."""
     c = Case(name)
-    m = _model(c)
+    m = case_model(c, precision='fp32')
     rays = _cuda(c.inputs)
     z, _ = m.ray_sampler.get_z_vals(rays['ray_dirs'], rays['ray_cam_loc'], m)
     assert m.ray_sampler.last_rounds == c.rounds
@@ -485,9 +464,8 @@ PER_SAMPLE = ('weights', 'sdf', 'z_vals', 'depth_vals', 'rgb')
 @pytest.mark.parametrize('name', ALL_CASES)
 def test_full_forward_against_golden(name, precision, errlog):
     c = Case(name)
-    m = _model(c, precision=precision)
-    m._noise = _cuda(c.noise) if c.noise else None
-    out = m(_cuda(c.inputs), c.indices.cuda(), if_pixel_input=c.pixel)
+    m = case_model(c, precision=precision)
+    out = run_pass(m, c.inputs, c.indices, c.noise, c.pixel)
     assert set(out) == set(c.out)
     assert m.ray_sampler.last_rounds == c.rounds
     for k, ref in c.out.items():
@@ -504,17 +482,14 @@ def test_full_forward_against_golden(name, precision, errlog):
 def test_full_gradients_against_golden(name, precision, errlog):
     from oracle import monosdf_oracle as mo
     c = Case(name)
-    m = _model(c, precision=precision)
-    m._noise = _cuda(c.noise)
-    out = m(_cuda(c.inputs), c.indices.cuda(), if_pixel_input=c.pixel)
+    m = case_model(c, precision=precision)
+    out = run_pass(m, c.inputs, c.indices, c.noise, c.pixel)
     loss = mo.probe_loss(out)
     test = 'gradients_golden.' + precision
     check(errlog, test, name, 'loss', abs(loss.item() - c.loss) / max(1.0, abs(c.loss)))
     loss.backward()
+    check_param_grads(errlog, test, name, m, c.grads, list(c.grads))
     params = dict(m.named_parameters())
-    for n, ref in c.grads.items():
-        assert params[n].grad is not None, n
-        check(errlog, test, name, n, rel_err(params[n].grad, ref))
     for n, ref in c.gdig.items():
         d = digest(params[n].grad)
         check(errlog, test, name, n + '(digest)', abs(d[0] - ref[0]).item() / (ref[1].item() + 1e-9))
@@ -540,7 +515,7 @@ def test_full_image_render_chunked(errlog):
     from oracle import monosdf_oracle as mo
     from monosdf_amd.utils import render
     c = Case('mlp_w64_image_eval')
-    m = _model(c)
+    m = case_model(c, precision='fp32')
     n_side = 12
     ys, xs = torch.meshgrid(torch.arange(n_side), torch.arange(n_side), indexing='ij')
     uv = torch.stack([xs.flatten() * 30.0 + 10.0, ys.flatten() * 30.0 + 12.0], -1)[None].float()
@@ -564,7 +539,7 @@ def test_sdf_volume_coarse_to_fine(golden_dir, errlog):
     z, spec, conf, state = volume_fixture(golden_dir)
     c = Case('mlp_w64_eval')
     assert spec['width'] == 64 and spec['jitter'] == c.spec['jitter']
-    m = _model(c)
+    m = case_model(c, precision='fp32')
     lo, hi = spec['grid_boundary']
     with torch.no_grad():
         fn = lambda p: m.implicit_network(p)[:, 0]
@@ -592,13 +567,9 @@ def test_configs0_uniform_sampler_plumbing(golden_dir, errlog):
     MonoSDFNetwork.forward composes them (reference network.py:532-562,603-611), against the fixture recorded from
     the reference's own UniformSampler + ImplicitNetwork + RenderingNetwork + volume_rendering."""
     from test_oracle_golden import plumbing_fixture
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     from monosdf_amd.model.ray_sampler import UniformSampler
     z, spec, conf, state, rays = plumbing_fixture(golden_dir)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict(state, strict=True)
-    m = m.cuda().eval()
+    m = build_model(conf, state, training=False)
     r = _cuda(rays)
     dirs, cam = r['ray_dirs'], r['ray_cam_loc']
     us = UniformSampler(conf['scene_bounding_sphere'], 0.0, spec['n_samples'], take_sphere_intersection=True)
@@ -649,30 +620,23 @@ def test_ragged_batches_against_oracle(n_rays, precision, errlog):
     """Batches that fill neither a wave (16 points) nor a workgroup (64): 1, 5 and 67 rays, training mode,
     forward + backward against the oracle on the same rays and the same random draws."""
     from oracle import config, monosdf_oracle as mo, synth
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     conf = config.mlp_config(width=64, depth=8)
     state = synth.make_state(conf, seed=3, jitter=0.3)
     rays = synth.make_rays(n_rays, seed=4, random_pose=True)
     noise = synth.make_noise(conf, n_rays, 128, seed=5)
-    model = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    model.load_state_dict(state, strict=True)
-    model = model.cuda().train().set_precision(precision)
-    model._noise = _cuda(noise)
+    model = build_model(conf, state, precision=precision)
     idx = torch.arange(n_rays)
-    out = model(_cuda(rays), idx.cuda(), if_pixel_input=True)
-    mo.probe_loss(out).backward()
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    out = run_pass(model, rays, idx, noise, loss=mo.probe_loss)
+    st = oracle_state(state, grad=True)
     ref = mo.render(st, conf, rays, idx, True, True, noise)
     mo.probe_loss(ref).backward()
     test, case = 'ragged.' + precision, '%d_rays' % n_rays
     for k in ('rgb_values', 'depth_values', 'normal_map', 'grad_theta', 'weights', 'sdf'):
         assert out[k].shape == ref[k].shape, k
         check(errlog, test, case, k, rel_err(out[k], ref[k]))
-    params = dict(model.named_parameters())
-    for n in ('implicit_network.lin4.weight_v', 'implicit_network.lin0.bias', 'rendering_network.lin1.weight_g',
-              'density.beta'):
-        check(errlog, test, case, n, rel_err(params[n].grad, st[n].grad))
+    names = ['implicit_network.lin4.weight_v', 'implicit_network.lin0.bias', 'rendering_network.lin1.weight_g',
+             'density.beta']
+    check_param_grads(errlog, test, case, model, {n: st[n].grad for n in names}, names)
 
 
 def test_ddp_wrapped_training_step_matches_plain():
@@ -683,8 +647,8 @@ def test_ddp_wrapped_training_step_matches_plain():
     import torch.distributed as dist
     from monosdf_amd.model.loss import MonoSDFLoss
     c = Case('mlp_w64_train')
-    plain = _model(c, training=True)
-    wrapped_inner = _model(c, training=True)
+    plain = case_model(c, training=True, precision='fp32')
+    wrapped_inner = case_model(c, training=True, precision='fp32')
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ.setdefault('MASTER_PORT', '29533')
     created = not dist.is_initialized()

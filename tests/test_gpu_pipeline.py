@@ -33,9 +33,8 @@ def _frames(n, side, seed):
 
 def test_training_render_and_volume_compose():
     import bench
-    from monosdf_amd.conf import ConfigTree
+    from harness import build_model
     from monosdf_amd.model.loss import MonoSDFLoss
-    from monosdf_amd.model.network import MonoSDFNetwork
     from monosdf_amd.utils import render
     from monosdf_amd.utils.ray_table import PixelRayTable
     from oracle import config
@@ -50,7 +49,7 @@ def test_training_render_and_volume_compose():
     table = PixelRayTable(poses, intr, (side, side), train_frames, **imgs)
     assert len(table) == (n_frames - 1) * side * side
     torch.manual_seed(0)
-    model = MonoSDFNetwork(ConfigTree.from_dict(config.mlp_config(64, 8))).cuda().train()
+    model = build_model(config.mlp_config(64, 8))
     loss_fn = MonoSDFLoss('torch.nn.L1Loss', eikonal_weight=0.05, smooth_weight=0.005, depth_weight=0.1,
                           normal_l1_weight=0.05, normal_cos_weight=0.05)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)

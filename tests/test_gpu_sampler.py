@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from harness import (assert_same_step, build_model, case_model as _model, run_pass, shared_weights, step_record,
+                     to_device)
 from helpers import Case, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -50,15 +52,6 @@ def _cdf_residual(cdf, z, x, u):
     lo = torch.where(on_edge, torch.gather(cdf, 1, lo_i.clamp(0, m - 1)), lin)
     hi = torch.where(on_edge, torch.gather(cdf, 1, (hi_i - 1).clamp(0, m - 1)), lin)
     return torch.maximum(lo - u, u - hi).clamp(min=0)
-
-
-def _model(case):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
-    m = MonoSDFNetwork(ConfigTree.from_dict(case.conf))
-    m.load_state_dict({k: v.clone() for k, v in case.state.items()}, strict=True)
-    m.train(case.training)
-    return m.cuda()
 
 
 @pytest.mark.parametrize('name', TRACED)
@@ -237,16 +230,13 @@ def test_error_bound_density_uniform_stage_vectors(golden_dir, errlog):
 
 
 def _run(model, case, speculate):
+    """One pass of the case in the given speculation mode as a step record (every output; gradients of the probe loss
+    when the case trains)."""
     from oracle import monosdf_oracle as mo
     model.speculate_rounds = speculate
     model.zero_grad(set_to_none=True)
-    model._noise = {k: v.cuda() for k, v in case.noise.items()} if case.noise else None
-    out = model({k: v.cuda() for k, v in case.inputs.items()}, case.indices.cuda(), if_pixel_input=case.pixel)
-    grads = None
-    if case.training:
-        mo.probe_loss(out).backward()
-        grads = {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
-    return {k: v.detach().clone() for k, v in out.items()}, grads
+    out = run_pass(model, case.inputs, case.indices, case.noise, case.pixel, mo.probe_loss if case.training else None)
+    return step_record(model, out)
 
 
 @pytest.mark.parametrize('name', ['mlp_w64_train', 'mlp_w64_eval', 'mlp_w64_train_sharp', 'mlp_w64_eval_k3',
@@ -258,22 +248,21 @@ def test_all_rounds_enqueued_equals_synchronous_path(name):
     c = Case(name)
     m = _model(c)
     K = m.ray_sampler.max_total_iters
-    ref_out, ref_grads = _run(m, c, False)
+    ref = _run(m, c, False)
     assert m.ray_sampler.last_rounds == c.rounds
     stats0 = dict(m.ray_sampler.stats)
-    out, grads = _run(m, c, 'all')
+    got = _run(m, c, 'all')
     assert m.ray_sampler.last_rounds == c.rounds
     d = {k: m.ray_sampler.stats[k] - stats0[k] for k in stats0}
     assert d == {'calls': 1, 'repeats': 0, 'idle_rounds': K - c.rounds}
-    for k in ref_out:
-        assert torch.equal(out[k], ref_out[k]), k
-    if c.training:
-        assert set(grads) == set(ref_grads)
-        for n in ref_grads:
-            if 'encoding' in n:          # hash-grid table: float sums in run-dependent order
-                assert rel_err(grads[n], ref_grads[n]) < 1e-5, n
-            else:                        # weight gradients are bitwise reproducible (fixed-order reduction)
-                assert torch.equal(grads[n], ref_grads[n]), n
+    for k in ref['out']:
+        assert torch.equal(got['out'][k], ref['out'][k]), k
+    assert set(got['grads']) == set(ref['grads']) and bool(ref['grads']) == c.training
+    for n, g in ref['grads'].items():
+        if 'encoding' in n:          # hash-grid table: float sums in run-dependent order
+            assert rel_err(got['grads'][n], g) < 1e-5, n
+        else:                        # weight gradients are bitwise reproducible (fixed-order reduction)
+            assert torch.equal(got['grads'][n], g), n
 
 
 @pytest.mark.parametrize('name,history', [('mlp_w64_train', [3]), ('mlp_w64_train', [1, 5, 2]), ('mlp_w64_train_k4', [1]),
@@ -283,10 +272,10 @@ def test_round_count_guessed_from_history(name, history):
     nothing; too few -> the pass is repeated with all rounds.  Either way the result is the synchronous path's."""
     c = Case(name)
     m = _model(c)
-    ref_out, ref_grads = _run(m, c, False)
+    ref = _run(m, c, False)
     stats0 = dict(m.ray_sampler.stats)
     m.ray_sampler._hist[0] = list(history)
-    out, grads = _run(m, c, True)
+    got = _run(m, c, True)
     assert m.ray_sampler.last_rounds == c.rounds
     d = {k: m.ray_sampler.stats[k] - stats0[k] for k in stats0}
     guess = max(history) if history else 1
@@ -294,11 +283,8 @@ def test_round_count_guessed_from_history(name, history):
         assert d == {'calls': 1, 'repeats': 0, 'idle_rounds': guess - c.rounds}
     else:
         assert d == {'calls': 2, 'repeats': 1, 'idle_rounds': m.ray_sampler.max_total_iters - c.rounds}
-    for k in ref_out:
-        assert torch.equal(out[k], ref_out[k]), k
-    if c.training:
-        for n in ref_grads:
-            assert torch.equal(grads[n], ref_grads[n]), n
+    assert bool(ref['grads']) == c.training
+    assert_same_step(ref, got)
     nxt = m.ray_sampler.guess_rounds()
     assert nxt >= c.rounds                                   # the next call will enqueue enough
     if guess < c.rounds:
@@ -311,7 +297,7 @@ def test_speculating_k_rounds(name):
     were, the samples equal the synchronous path's, whatever k."""
     c = Case(name)
     m = _model(c)
-    rays = {k: v.cuda() for k, v in c.inputs.items()}
+    rays = to_device(c.inputs)
     z_ref, _, _ = m.ray_sampler.sample(rays['ray_dirs'], rays['ray_cam_loc'], m, want_points=False)
     assert m.ray_sampler.last_rounds == c.rounds
     for k in range(1, m.ray_sampler.max_total_iters + 1):
@@ -328,7 +314,7 @@ def test_global_round_decision_single_rank():
     import torch.distributed as dist
     c = Case('mlp_w64_eval_k3')
     m = _model(c)
-    ref, _ = _run(m, c, False)
+    ref = _run(m, c, False)['out']
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ.setdefault('MASTER_PORT', '29541')
     created = not dist.is_initialized()
@@ -337,7 +323,7 @@ def test_global_round_decision_single_rank():
     try:
         m.ray_sampler.global_rounds = True
         for spec in (False, True):
-            out, _ = _run(m, c, spec)
+            out = _run(m, c, spec)['out']
             assert m.ray_sampler.last_rounds == c.rounds
             for k in ref:
                 assert torch.equal(out[k], ref[k]), k
@@ -357,16 +343,12 @@ def test_uninjected_draws_replayed(speculate, with_reuse):
     Sizes: 10 rays (off the 4 rays of a workgroup), 66 dense samples (over one 64-lane trip), no cut of the pool
     on a round number, 10 * 7 = 70 >= 64 dense-set points so that an SdfReuse has rows to reuse and the column
     table is drawn before the first launch."""
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     from oracle import config, synth
     N, n_eval, n_final, n_extra, K, seed = 10, 66, 33, 7, 2, 1234
     S = n_final + n_extra + 2
     conf = config.mlp_config(64, 8, beta=0.1)
     conf['ray_sampler'].update(N_samples_eval=n_eval, N_samples=n_final, N_samples_extra=n_extra, max_total_iters=K)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict(synth.make_state(conf, seed=5, jitter=0.3), strict=True)
-    m = m.cuda().train()
+    m = build_model(conf, synth.make_state(conf, seed=5, jitter=0.3))
     smp, net = m.ray_sampler, m.implicit_network
     assert (smp.N_samples_eval, smp.N_samples, smp.N_samples_extra, smp.max_total_iters) == (n_eval, n_final, n_extra, K)
     rays = synth.make_rays(N, seed=13, random_pose=True)
@@ -381,8 +363,7 @@ def test_uninjected_draws_replayed(speculate, with_reuse):
         assert speculate == 0 or smp.confirm()
         return z.clone(), z_eik.clone(), x_all.clone(), smp.last_rounds
 
-    net.share(dev)
-    try:
+    with shared_weights(net, dev):
         torch.manual_seed(seed)
         m._noise = None
         drawn = sample()
@@ -395,8 +376,6 @@ def test_uninjected_draws_replayed(speculate, with_reuse):
                     'extra_idx': torch.stack([torch.randperm(n_eval * (k + 1))[:n_extra] for k in range(K)])}
         assert m._noise['eik_uniform'].dtype == torch.float32 and m._noise['extra_idx'].shape == (K, n_extra)
         injected = sample()
-    finally:
-        net.unshare()
     assert drawn[0].shape == (N, S) and drawn[1].shape == (N, 1) and drawn[2].shape == (N * S + 4 * N, 3)
     for name, a, b in zip(('z_vals', 'z_eik', 'x_all'), drawn, injected):
         assert torch.equal(a, b), name

@@ -10,45 +10,14 @@ import functools
 import pytest
 import torch
 
+from harness import assert_same_step, oracle_state, run_pass, shared_weights, step_record, switched, to_device
 from helpers import check, rel_err
-from oracle import config, synth
+from reuse_cases import N_EVAL, N_EXTRA, NETS, OUT_KEYS, conf_state as _conf_state, inputs as _inputs, model as _model
 
 pytestmark = pytest.mark.gpu
 
-NETS = {'w64_skip': (64, True), 'w64_noskip': (64, False), 'w256_skip': (256, True)}
 RAYS = (2, 3, 5, 16)
 CASES = [(net, n) for net in sorted(NETS) for n in RAYS]
-N_EVAL, N_EXTRA = 128, 32
-OUT_KEYS = ('rgb', 'rgb_values', 'depth_values', 'z_vals', 'depth_vals', 'sdf', 'weights', 'grad_theta',
-            'grad_theta_nei', 'normal_map')
-
-
-@functools.lru_cache(maxsize=None)
-def _conf_state(net, beta):
-    width, skip = NETS[net]
-    conf = config.mlp_config(width, 8, beta=beta)
-    if not skip:
-        conf['implicit_network']['skip_in'] = []
-    return conf, synth.make_state(conf, seed=5, jitter=0.3)
-
-
-def _model(net, beta):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
-    conf, state = _conf_state(net, beta)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    return m.cuda().train()
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(net, n, beta, table):
-    conf, _ = _conf_state(net, beta)
-    # the rays of the sharp state (`table`) are seeds at which the oracle's sampler needs exactly two rounds in all
-    # twelve cases (with most seeds the 256-wide state converges in one round for 2 or 3 rays)
-    rays = synth.make_rays(n, seed=(50 if table else 3) + n, random_pose=True)
-    noise = synth.make_noise_table(conf, n, seed=7) if table else synth.make_noise(conf, n, N_EVAL, seed=7)
-    return rays, noise
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,27 +28,12 @@ def _run(net, n, reuse_on, beta=0.1, speculate=True, table=False):
     rays, noise = _inputs(net, n, beta, table)
     m = _model(net, beta)
     m.speculate_rounds = speculate
-    m._noise = {k: v.cuda() for k, v in noise.items()}
-    was, ops.REUSE_SAMPLER_H = ops.REUSE_SAMPLER_H, reuse_on
-    try:
-        out = m({k: v.cuda() for k, v in rays.items()}, torch.arange(n).cuda(), if_pixel_input=True)
+    with switched(ops, 'REUSE_SAMPLER_H', reuse_on):
+        out = run_pass(m, rays, torch.arange(n), noise)
         loss = mo.probe_loss(out)
         loss.backward()
-    finally:
-        ops.REUSE_SAMPLER_H = was
     torch.cuda.synchronize()
-    return {'out': {k: out[k].detach().clone() for k in OUT_KEYS}, 'loss': loss.detach().clone(),
-            'grads': {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None},
-            'rounds': m.ray_sampler.last_rounds, 'repeats': m.ray_sampler.stats['repeats']}
-
-
-def _assert_same_step(a, b):
-    assert sorted(a['out']) == sorted(b['out']) and sorted(a['grads']) == sorted(b['grads'])
-    for k in a['out']:
-        assert torch.equal(a['out'][k], b['out'][k]), k
-    assert torch.equal(a['loss'], b['loss'])
-    for k in a['grads']:
-        assert torch.equal(a['grads'][k], b['grads'][k]), k
+    return step_record(m, out, loss, OUT_KEYS)
 
 
 @pytest.mark.parametrize('net,n', CASES)
@@ -88,7 +42,7 @@ def test_reuse_on_and_off_are_bit_identical(net, n):
     on, off = _run(net, n, True), _run(net, n, False)
     assert on['rounds'] == off['rounds'] == 1 and on['repeats'] == 0
     assert len(on['grads']) >= 20
-    _assert_same_step(on, off)
+    assert_same_step(on, off)
 
 
 @pytest.mark.parametrize('net,n', CASES)
@@ -97,7 +51,7 @@ def test_outputs_agree_with_the_oracle(net, n, errlog):
     from oracle import monosdf_oracle as mo
     conf, state = _conf_state(net, 0.1)
     rays, noise = _inputs(net, n, 0.1, False)
-    ref = mo.render({k: v.clone() for k, v in state.items()}, conf, rays, torch.arange(n), True, True, noise)
+    ref = mo.render(oracle_state(state), conf, rays, torch.arange(n), True, True, noise)
     out = _run(net, n, True)['out']
     for k in ('rgb_values', 'depth_values', 'normal_map', 'grad_theta', 'weights', 'sdf'):
         check(errlog, 'sdf_reuse', '%s.%d' % (net, n), k, rel_err(out[k], ref[k].detach()))
@@ -113,9 +67,9 @@ def test_two_round_state_in_every_speculation_mode(net, n):
     assert hist['rounds'] == 2 and hist['repeats'] == 1
     sync, every = _run(net, n, True, beta, False, True), _run(net, n, True, beta, 'all', True)
     assert sync['rounds'] == every['rounds'] == hist['rounds'] and sync['repeats'] == every['repeats'] == 0
-    _assert_same_step(hist, sync)
-    _assert_same_step(hist, every)
-    _assert_same_step(hist, _run(net, n, False, beta, True, True))
+    assert_same_step(hist, sync)
+    assert_same_step(hist, every)
+    assert_same_step(hist, _run(net, n, False, beta, True, True))
 
 
 @pytest.mark.parametrize('net,n', CASES)
@@ -129,14 +83,13 @@ def test_saved_rows_coordinates_and_skipped_products(net, n):
     from monosdf_amd.model.ray_sampler import ErrorBoundSampler
     rays, noise = _inputs(net, n, 0.1, False)
     m = _model(net, 0.1)
-    m._noise = {k: v.cuda() for k, v in noise.items()}
+    m._noise = to_device(noise)
     dev = torch.device('cuda', torch.cuda.current_device())
     sdfnet, smp = m.implicit_network, m.ray_sampler
     S = smp.N_samples + N_EXTRA + 2
     P, n_ext = n * S + 4 * n, n * N_EXTRA
     d, o = rays['ray_dirs'].cuda().contiguous(), rays['ray_cam_loc'].cuda().contiguous()
-    sdfnet.share(dev)
-    try:
+    with shared_weights(sdfnet, dev):
         fused, _, _, wpack, bpack = sdfnet.packed(dev)
         beta0 = ops.effective_beta(m.density.beta, m.density.beta_min_f)
         reuse = sdfnet.sdf_reuse(dev, n, S, N_EXTRA, 4 * n, True)
@@ -204,5 +157,3 @@ def test_saved_rows_coordinates_and_skipped_products(net, n):
         same = torch.ones(n * S, dtype=torch.bool, device=dev)
         same[rm[0]] = False
         assert torch.equal(sdf3[same], sdf_all[same]) and torch.equal(nrm3[same], nrm[same])
-    finally:
-        sdfnet.unshare()

@@ -6,6 +6,7 @@ same code of the oracle with other sizes."""
 import pytest
 import torch
 
+from harness import build_model, check_param_grads, oracle_grads, oracle_state, run_pass, switched
 from helpers import TOL, check, rel_err
 from oracle import config, synth
 
@@ -14,16 +15,25 @@ pytestmark = pytest.mark.gpu
 # (width, depth): 48 = 3 tiles (odd), 100 = 7 tiles with 12 padded slots, 176 = 11 tiles, 256 with 2 layers (the
 # hash-grid configuration's MLP without the grid)
 SHAPES = [(48, 2), (48, 5), (100, 3), (100, 8), (176, 5), (256, 2)]
+OUT_KEYS = ('rgb_values', 'depth_values', 'normal_map', 'weights', 'sdf', 'grad_theta')
 
 
-def _build(width, depth, precision):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
+def _build(width, depth, precision, training=True):
     conf = config.mlp_config(width, depth)
     state = synth.make_state(conf, seed=width + depth, jitter=0.3)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    return conf, state, m.cuda().set_precision(precision)
+    return conf, state, build_model(conf, state, training, precision=precision)
+
+
+def _training_pass_against(ref, st, test, case, errlog, m, rays, idx, noise, transform=None):
+    """One training pass on the rays and draws the oracle rendered `ref` from (its state `st`): OUT_KEYS, then the
+    gradients of the probe loss for every parameter the oracle's loss reaches."""
+    from oracle import monosdf_oracle as mo
+    out = run_pass(m, rays, idx, noise)
+    for k in OUT_KEYS:
+        check(errlog, test, case, k, rel_err(out[k], ref[k]))
+    g_o = oracle_grads(st, ref)
+    mo.probe_loss(out).backward()
+    check_param_grads(errlog, test, case, m, g_o, transform=transform)
 
 
 # the bf16x6 core on the generic widths too (run-time K-block counts, chunks of one out tile): same bars, same rows
@@ -32,13 +42,12 @@ def _build(width, depth, precision):
 def test_sdf_network_forward_gradient_and_double_backward(width, depth, precision, errlog):
     from oracle import monosdf_oracle as mo
     conf, state, m = _build(width, depth, precision)
-    m.train()
     g = torch.Generator().manual_seed(11)
     P = 64 * 3 + 21                                    # ragged last tile
     x = (torch.rand(P, 3, generator=g) * 2 - 1) * 1.2
     F = conf['feature_vector_size']
     ca, cb, cc = torch.randn(P, 1, generator=g), torch.randn(P, F, generator=g) * 0.1, torch.randn(P, 3, generator=g)
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    st = oracle_state(state, grad=True)
     sdf_o, feat_o, grad_o = mo.get_outputs(st, conf, x)
     sdf, feat, grad = m.implicit_network.get_outputs(x.cuda())
     assert rel_err(sdf, sdf_o) < TOL and rel_err(feat, feat_o) < TOL and rel_err(grad, grad_o) < TOL
@@ -47,10 +56,8 @@ def test_sdf_network_forward_gradient_and_double_backward(width, depth, precisio
     g_o = torch.autograd.grad(loss_o, [st[n] for n in names])
     loss = (ca.cuda() * sdf).sum() + (cb.cuda() * feat).sum() + (cc.cuda() * grad).sum()
     loss.backward()
-    params = dict(m.named_parameters())
-    for n, go in zip(names, g_o):
-        check(errlog, 'shapes_double_backward' + ('' if precision == 'fp32' else '.' + precision), '%dx%d' % (depth, width),
-              n, rel_err(params[n].grad, go))
+    check_param_grads(errlog, 'shapes_double_backward' + ('' if precision == 'fp32' else '.' + precision),
+                      '%dx%d' % (depth, width), m, dict(zip(names, g_o)), names)
 
 
 @pytest.mark.parametrize('width,depth', [(48, 5), (100, 3), (176, 5)])
@@ -58,26 +65,13 @@ def test_training_forward_and_gradients(width, depth, errlog):
     """The whole pass (sampler, both networks, compositor, eikonal block) and the gradients of the probe loss."""
     from oracle import monosdf_oracle as mo
     conf, state, m = _build(width, depth, 'fp32')
-    m.train()
     n = 24
     rays = synth.make_rays(n, seed=3, random_pose=True)
     noise = synth.make_noise(conf, n, 128, seed=5)
     idx = torch.arange(n) % 7
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    st = oracle_state(state, grad=True)
     ref = mo.render(st, conf, rays, idx, True, True, noise)
-    m._noise = {k: v.cuda() for k, v in noise.items()}
-    out = m({k: v.cuda() for k, v in rays.items()}, idx.cuda(), if_pixel_input=True)
-    case = '%dx%d' % (depth, width)
-    for k in ('rgb_values', 'depth_values', 'normal_map', 'weights', 'sdf', 'grad_theta'):
-        check(errlog, 'shapes_training', case, k, rel_err(out[k], ref[k]))
-    loss_o = mo.probe_loss(ref)
-    names = [k for k, v in st.items() if v.requires_grad]
-    g_o = dict(zip(names, torch.autograd.grad(loss_o, [st[k] for k in names], allow_unused=True)))
-    mo.probe_loss(out).backward()
-    for k, p in m.named_parameters():
-        if g_o.get(k) is None:
-            continue
-        check(errlog, 'shapes_training', case, k, rel_err(p.grad, g_o[k]))
+    _training_pass_against(ref, st, 'shapes_training', '%dx%d' % (depth, width), errlog, m, rays, idx, noise)
 
 
 def test_too_wide_network_is_refused():
@@ -88,14 +82,10 @@ def test_too_wide_network_is_refused():
 
 
 def _variant(edit, seed=21):
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     conf = config.mlp_config(64, 8)
     edit(conf)
     state = synth.make_state(conf, seed=seed, jitter=0.3)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    return conf, state, m.cuda()
+    return conf, state, build_model(conf, state)
 
 
 def _set(section, **kw):
@@ -134,12 +124,8 @@ def _relu_units_near_zero(fn, thresh=1e-6):
     def spy(h):
         masks.append((h.detach().abs().reshape(-1, h.shape[-1]).min(0)[0] < thresh))
         return real(h)
-    torch.relu = spy
-    try:
-        res = fn()
-    finally:
-        torch.relu = real
-    return res, masks
+    with switched(torch, 'relu', spy):
+        return fn(), masks
 
 
 @pytest.mark.parametrize('name', sorted(VARIANTS))
@@ -149,33 +135,25 @@ def test_config_options_against_oracle(name, errlog):
     lists the comparison (`options|<variant>|<tensor>`)."""
     from oracle import monosdf_oracle as mo
     conf, state, m = _variant(VARIANTS[name], seed=21)
-    m.train()
     n = 16
     rays = synth.make_rays(n, seed=6, random_pose=True)
     noise = synth.make_noise(conf, n, 128, seed=8)
     idx = torch.arange(n) % 5
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    st = oracle_state(state, grad=True)
     # weight seed 21 puts one ReLU input of the colour network's first layer at 9.9e-8 in the 'no_skip' network: the rows
     # of such units are left out of that layer's gradient comparison (the unit is found in the ORACLE's pre-activations)
     ref, near_zero = _relu_units_near_zero(lambda: mo.render(st, conf, rays, idx, True, True, noise))
-    m._noise = {k: v.cuda() for k, v in noise.items()}
-    out = m({k: v.cuda() for k, v in rays.items()}, idx.cuda(), if_pixel_input=True)
-    for k in ('rgb_values', 'depth_values', 'normal_map', 'weights', 'sdf', 'grad_theta'):
-        check(errlog, 'options', name, k, rel_err(out[k], ref[k]))
-    names = [k for k, v in st.items() if v.requires_grad]
-    g_o = dict(zip(names, torch.autograd.grad(mo.probe_loss(ref), [st[k] for k in names], allow_unused=True)))
-    mo.probe_loss(out).backward()
-    for k, p in m.named_parameters():
-        if g_o.get(k) is None:
-            continue
-        g, gr = p.grad.detach().cpu(), g_o[k]
+
+    def without_switching_units(k, g, gr):
+        g = g.detach().cpu()
         if k.startswith('rendering_network.lin'):
             layer = int(k.split('.')[1][3:])
             if layer < len(near_zero) and bool(near_zero[layer].any()):
                 keep = ~near_zero[layer]
                 assert int(keep.sum()) >= keep.numel() - 4, 'more than four units at a ReLU switch: pick another seed'
                 g, gr = g[keep], gr[keep]
-        check(errlog, 'options', name, k, rel_err(g, gr))
+        return g, gr
+    _training_pass_against(ref, st, 'options', name, errlog, m, rays, idx, noise, transform=without_switching_units)
 
 
 def test_wide_positional_encoding_is_refused():
@@ -199,8 +177,6 @@ def test_sampler_options_against_oracle(name, errlog):
     bisection steps, 5 rounds): a sharp state (beta 0.01, 2+ rounds) in eval mode -- z_vals and the rendered values
     against the oracle -- or a clear refusal."""
     from oracle import monosdf_oracle as mo
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     conf = config.mlp_config(64, 8, beta=0.01)
     conf['ray_sampler'].update(SAMPLER_VARIANTS[name])
     state = synth.make_state(conf, seed=31, jitter=0.1)
@@ -208,15 +184,13 @@ def test_sampler_options_against_oracle(name, errlog):
     rays = synth.make_rays(n, seed=9, random_pose=True)
     idx = torch.arange(n) % 5
     try:
-        m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-        m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-        m = m.cuda().eval()
+        m = build_model(conf, state, training=False)
         with torch.no_grad():
-            out = m({k: v.cuda() for k, v in rays.items()}, idx.cuda(), if_pixel_input=True)
+            out = run_pass(m, rays, idx)
     except (RuntimeError, NotImplementedError, ValueError) as e:
         assert 'monosdf_amd' in str(e), e          # refused by this package, with a reason
         pytest.skip('refused: %s' % e)
-    ref = mo.render({k: v.clone() for k, v in state.items()}, conf, rays, idx, True, False, None)   # needs autograd
+    ref = mo.render(oracle_state(state), conf, rays, idx, True, False, None)   # needs autograd
     ref = {k: v.detach() for k, v in ref.items()}
     assert out['z_vals'].shape == ref['z_vals'].shape
     far = mo.sampler_far(conf)
@@ -238,38 +212,24 @@ def test_hash_grid_model_variants_against_oracle(name, errlog):
     encoding + MLP node, embedding gradients included) against the oracle.  Hash arithmetic: parity unpinned by
     reference outputs (README) -- this pins the wiring for other table geometries."""
     from oracle import monosdf_oracle as mo
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     g = GRID_VARIANTS[name]
     conf = config.grid_config(64, 0.1, g['num_levels'], g['level_dim'], g['logmap'], g['base_size'], g['end_size'])
     state = synth.make_state(conf, seed=41, jitter=0.3)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    m = m.cuda().train()
+    m = build_model(conf, state)
     n = 12
     rays = synth.make_rays(n, seed=4, random_pose=True)
     noise = synth.make_noise(conf, n, 128, seed=6)
     idx = torch.arange(n) % 5
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    st = oracle_state(state, grad=True)
     ref = mo.render(st, conf, rays, idx, True, True, noise)
-    m._noise = {k: v.cuda() for k, v in noise.items()}
-    out = m({k: v.cuda() for k, v in rays.items()}, idx.cuda(), if_pixel_input=True)
-    for k in ('rgb_values', 'depth_values', 'normal_map', 'weights', 'sdf', 'grad_theta'):
-        check(errlog, 'grid_variants', name, k, rel_err(out[k], ref[k]))
-    names = [k for k, v in st.items() if v.requires_grad]
-    g_o = dict(zip(names, torch.autograd.grad(mo.probe_loss(ref), [st[k] for k in names], allow_unused=True)))
-    mo.probe_loss(out).backward()
-    for k, p in m.named_parameters():
-        if g_o.get(k) is not None:
-            check(errlog, 'grid_variants', name, k, rel_err(p.grad, g_o[k]))
+    _training_pass_against(ref, st, 'grid_variants', name, errlog, m, rays, idx, noise)
 
 
 @pytest.mark.parametrize('P', [0, 1, 15, 16, 17, 63, 65])
 def test_tiny_and_empty_point_sets(P):
     """Fewer points than a wave tile (16) / a workgroup (64), and none at all: the public evaluation methods."""
     from oracle import monosdf_oracle as mo
-    conf, state, m = _build(64, 8, 'fp32')
-    m.eval()
+    conf, state, m = _build(64, 8, 'fp32', training=False)
     g = torch.Generator().manual_seed(P + 1)
     x = (torch.rand(P, 3, generator=g) * 2 - 1)
     net = m.implicit_network
@@ -281,7 +241,7 @@ def test_tiny_and_empty_point_sets(P):
     assert feat.shape == (P, conf['feature_vector_size'])
     if P == 0:
         return
-    st = {k: v.clone() for k, v in state.items()}
+    st = oracle_state(state)
     sdf_o, feat_o, grad_o = mo.get_outputs(st, conf, x, create_graph=False)
     assert rel_err(sdf, sdf_o) < TOL and rel_err(feat, feat_o) < TOL and rel_err(grad, grad_o) < TOL
     assert rel_err(vals, mo.get_sdf_vals(st, conf, x)) < TOL
@@ -292,13 +252,9 @@ def test_tiny_and_empty_point_sets_grid_model(P):
     """The same on the hash-grid network (encoder node forms + level-major feature tensors): an empty point set has
     NULL tensors and must come back as empty outputs and an all-zero table gradient, not as an argument error."""
     from oracle import monosdf_oracle as mo
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     conf = config.grid_config(64, 0.1, 4, 2, 11, 8, 64)
     state = synth.make_state(conf, seed=5, jitter=0.3)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    m = m.cuda().train()
+    m = build_model(conf, state)
     net = m.implicit_network
     g = torch.Generator().manual_seed(P + 3)
     x = (torch.rand(P, 3, generator=g) * 2 - 1)
@@ -313,7 +269,7 @@ def test_tiny_and_empty_point_sets_grid_model(P):
     if P == 0:
         assert float(emb.grad.abs().max()) == 0.0
         return
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    st = oracle_state(state, grad=True)
     sdf_o, feat_o, grad_o = mo.get_outputs(st, conf, x)
     assert rel_err(sdf, sdf_o) < TOL and rel_err(feat, feat_o) < TOL and rel_err(grad, grad_o) < TOL
     assert rel_err(vals, mo.get_sdf_vals(st, conf, x)) < TOL
@@ -337,8 +293,6 @@ def test_input_and_output_modes_against_oracle(name, errlog):
     golden holds together."""
     import numpy as np
     from oracle import monosdf_oracle as mo
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     image, training, white, code, hdr = MODE_VARIANTS[name]
     conf = config.mlp_config(64, 8)
     conf['white_bkgd'] = white
@@ -359,21 +313,16 @@ def test_input_and_output_modes_against_oracle(name, errlog):
         inputs = synth.make_rays(n, seed=7, random_pose=True)
         idx = torch.arange(n) % 7
     noise = synth.make_noise(conf, n, 128, seed=9) if training else None
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf), if_hdr=hdr)
-    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
-    m = m.cuda().train(training)
-    st = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in state.items()}
+    m = build_model(conf, state, training, if_hdr=hdr)
+    st = oracle_state(state, grad=True)
     ref = mo.render(st, conf, inputs, idx, not image, training, noise, if_hdr=hdr)
-    m._noise = {k: v.cuda() for k, v in noise.items()} if noise else None
-    out = m({k: v.cuda() for k, v in inputs.items()}, idx.cuda(), if_pixel_input=not image)
+    out = run_pass(m, inputs, idx, noise, pixel=not image)
     assert set(out) == set(ref)
     for k in ref:
         assert out[k].shape == ref[k].shape, k
         check(errlog, 'modes', name, k, rel_err(out[k], ref[k]))
     if training:
-        names = [k for k, v in st.items() if v.requires_grad]
-        g_o = dict(zip(names, torch.autograd.grad(mo.probe_loss(ref), [st[k] for k in names], allow_unused=True)))
+        g_o = oracle_grads(st, ref)
         mo.probe_loss(out).backward()
-        for k, p in m.named_parameters():
-            if g_o.get(k) is not None and p.grad is not None:
-                check(errlog, 'modes', name, k, rel_err(p.grad, g_o[k]))
+        # the one comparison that leaves a parameter without a GPU gradient out instead of failing
+        check_param_grads(errlog, 'modes', name, m, g_o, allow_missing=True)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from harness import build_model, run_pass, to_device as cuda
 from helpers import check, digest
 from oracle import config, synth
 
@@ -39,20 +40,15 @@ def _conf(spec):
 def test_training_trajectory_matches_reference(name, precision, golden_dir, errlog):
     if precision != 'fp32' and name == 'traj_grid_small':
         pytest.skip('the hash-grid run is about the table scatter, not the matrix core')
-    from monosdf_amd.conf import ConfigTree
     from monosdf_amd.model.loss import MonoSDFLoss
-    from monosdf_amd.model.network import MonoSDFNetwork
     z = np.load('%s/%s.npz' % (golden_dir, name))
     spec = dict(ast.literal_eval(bytes(z['spec']).decode()))
     conf = _conf(spec)
-    state = synth.make_state(conf, seed=spec['weight_seed'], jitter=spec['jitter'])
-    model = MonoSDFNetwork(ConfigTree.from_dict(conf))
-    model.load_state_dict(state, strict=True)
-    model = model.cuda().set_precision(precision)
+    model = build_model(conf, synth.make_state(conf, seed=spec['weight_seed'], jitter=spec['jitter']),
+                        precision=precision)
     loss_fn = MonoSDFLoss(rgb_loss='torch.nn.L1Loss', **spec['loss'])
     opt = torch.optim.Adam(model.parameters(), lr=spec['lr'])
     n = spec['n_rays']
-    cuda = lambda d: {k: v.cuda() for k, v in d.items()}
     held = synth.make_rays(spec['held_out_rays'], seed=spec['held_out_seed'], random_pose=True)
     held_gt = synth.analytic_targets(held)['rgb'][0].cuda()
     held = cuda(held)
@@ -62,9 +58,8 @@ def test_training_trajectory_matches_reference(name, precision, golden_dir, errl
     for step in range(spec['steps']):
         rays = synth.make_rays(n, seed=spec['ray_seed0'] + step, random_pose=True)
         gt = synth.analytic_targets(rays)
-        model._noise = cuda(synth.make_noise_table(conf, n, seed=spec['noise_seed0'] + step))
         model.train()
-        out = model(cuda(rays), idx, if_pixel_input=True)
+        out = run_pass(model, rays, idx, synth.make_noise_table(conf, n, seed=spec['noise_seed0'] + step))
         res = loss_fn(out, gt, if_pixel_input=True)
         opt.zero_grad()
         res['loss'].backward()

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from abi_cases import mirrors as _mirrors
+from harness import build_model
 from helpers import Case
 from oracle import config, monosdf_oracle as mo, synth
 
@@ -384,19 +385,14 @@ def test_color_wgrad_program_covers_every_weight_once():
 
 def test_state_dict_is_interchangeable_with_the_reference_layout():
     """Keys / shapes of our modules equal the reference's (golden synth states use the reference's key names)."""
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     for name in ['mlp_w64_eval', 'gridless_w128_train', 'grid_small_eval', 'mlp_w64_code_train']:
         c = Case(name)
-        m = MonoSDFNetwork(ConfigTree.from_dict(c.conf))
-        m.load_state_dict(c.state, strict=True)
+        m = build_model(c.conf, c.state, device=None)
         assert set(m.state_dict()) == set(c.state)
 
 
 def test_cpu_tensors_fail_loudly():
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
-    m = MonoSDFNetwork(ConfigTree.from_dict(config.mlp_config(64)))
+    m = build_model(config.mlp_config(64), device=None)
     with pytest.raises(RuntimeError):
         m.implicit_network.get_outputs(torch.zeros(4, 3))
 
@@ -496,10 +492,8 @@ def test_grid_network_parameter_groups_as_the_runner_builds_them():
     its three Adam groups from (training/monosdf_train.py:210-219: encoding at lr x lr_factor_for_grid, net, density):
     disjoint, together exactly implicit_network.parameters(), and one optimiser step moves every group by ITS learning
     rate (Adam's first step is lr * sign(g))."""
-    from monosdf_amd.conf import ConfigTree
-    from monosdf_amd.model.network import MonoSDFNetwork
     conf = config.grid_config(64, 0.1, 4, 2, 10, 16, 64)
-    m = MonoSDFNetwork(ConfigTree.from_dict(conf))
+    m = build_model(conf, device=None)
     net = m.implicit_network
     grid, mlp = list(net.grid_parameters()), list(net.mlp_parameters())
     ids = lambda ps: {id(p) for p in ps}

@@ -11,6 +11,7 @@ import torch
 
 from oracle import monosdf_oracle as mo
 from oracle import config, synth
+from harness import oracle_state
 from helpers import ALL_CASES, Case, digest, rel_err
 
 TOL = 2e-4
@@ -19,7 +20,7 @@ TOL = 2e-4
 @pytest.mark.parametrize('name', ALL_CASES)
 def test_forward_and_grads_match_reference(name):
     c = Case(name)
-    state = {k: v.clone().requires_grad_(v.dtype.is_floating_point) for k, v in c.state.items()}
+    state = oracle_state(c.state, grad=True)
     trace = {}
     out = mo.render(state, c.conf, c.inputs, c.indices, c.pixel, c.training, c.noise,
                     if_hdr=c.spec.get('if_hdr', False))

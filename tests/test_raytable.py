@@ -75,15 +75,14 @@ def test_pixel_batches_on_the_device_match_the_reference(errlog):
 @pytest.mark.gpu
 def test_pixel_batch_feeds_the_model():
     """A batch from the table goes straight into MonoSDFNetwork.forward(if_pixel_input=True) and the fused loss."""
-    from monosdf_amd.conf import ConfigTree
+    from harness import build_model
     from monosdf_amd.model.loss import MonoSDFLoss
-    from monosdf_amd.model.network import MonoSDFNetwork
     from monosdf_amd.utils.ray_table import PixelRayTable
     from oracle import config
     z, spec, t = _fixture()
     imgs = {k: t('in.' + k) for k in ('rgb', 'depth', 'mask', 'normal')}
     tab = PixelRayTable(t('in.pose'), t('in.intrinsics'), spec['img_res'], spec['frames'], **imgs)
-    m = MonoSDFNetwork(ConfigTree.from_dict(config.mlp_config(64, 8))).cuda().train()
+    m = build_model(config.mlp_config(64, 8))
     indices, sample, gt = tab.batch(torch.randint(len(tab), (32,)).cuda())
     out = m(sample, indices.long(), if_pixel_input=True)
     loss = MonoSDFLoss('torch.nn.L1Loss', eikonal_weight=0.05)(out, {k: v[None] for k, v in gt.items()},
